@@ -16,7 +16,12 @@ lists) are resident in HBM before the timed region; the timed region contains
 the event binning, every forward pass, the loss, the whole backward, the
 all-reduce and the optimizer -- nothing is skipped or cached.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): metric, value, unit, ms_per_step (the
+milliseconds one timed step took), dtype, config.  `--dump-outputs DIR` also writes what the last timed step left to its caller
+(loss, parameters, Adam moments, recurrent state) as DIR/<name>.npy; that step then starts from the run's initial training
+state (rewind_to_start), so that the files are the same from run to run up to the rounding of float atomics.  Everything else the benchmark measures -- repeated timing
+blocks, per-kernel and roofline figures, the IWE sweep, the CPU baseline, the other configurations, the alive workloads, the
+other FireNets -- runs with `--full` only.  Extra objects of a `--full` line:
   roofline      dominant kernel: algorithmic bytes per launch / mean launch
                 duration against the 8 TB/s HBM peak (the bf16x3 kernels are
                 HBM bound; --precision fp32: FLOP against the fp32-MFMA peak).
@@ -240,6 +245,102 @@ def capture_step_graphs(model, lossf, opt, dp, pool, stream, reps=None, capture_
     return graphs
 
 
+def _tensor_leaves(x, name, out):
+    """Flatten nested lists / tuples / dicts of tensors (None entries dropped) into [(name_i_j, tensor)]."""
+    if torch.is_tensor(x):
+        out.append((name, x))
+    elif isinstance(x, dict):
+        for k in sorted(x):
+            _tensor_leaves(x[k], f"{name}_{k}", out)
+    elif isinstance(x, (list, tuple)):
+        for i, v in enumerate(x):
+            _tensor_leaves(v, f"{name}_{i}", out)
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # all files of one --dump-outputs together (8 bytes counted per element)
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: what the last timed step handed to its caller, one `path/<name>.npy` per tensor of `outputs` (a dict of
+    tensors or nested lists of tensors), float32 as it is, int32 (bit fields) as one float32 per bit, every other dtype as float64.  A tensor above the per-array cap
+    is written as a fixed sample of its flattened elements (sorted indices drawn by numpy's default_rng(0), the same for
+    every run of the same shapes); the cap is the largest power of two that keeps the whole dump under DUMP_BUDGET_BYTES."""
+    leaves = []
+    _tensor_leaves(outputs, "", leaves)
+    cap = 1 << 22
+    while sum(min(t.numel() * (32 if t.dtype == torch.int32 else 1), cap) for _, t in leaves) * 8 > DUMP_BUDGET_BYTES:
+        cap >>= 1
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    written = {}
+    for name, t in leaves:
+        t = t.detach()
+        if t.dtype == torch.int32:  # packed spike words: one 0 / 1 value per bit, lowest bit first
+            t = ((t.unsqueeze(-1) >> torch.arange(32, device=t.device, dtype=torch.int32)) & 1).to(torch.float32)
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        if t.dtype != torch.float32:
+            t = t.to(torch.float64)
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, name.lstrip("_") + ".npy"), a)
+        written[name.lstrip("_")] = list(a.shape)
+    return written
+
+
+def rewind_to_start(opt, params0, states):
+    """--dump-outputs: put the training state back where the run began -- the seeded initial parameters, zero Adam moments and
+    step count, a zero recurrent state in the tensors `states` the next step reads -- so that the step that follows computes
+    the same outputs in every run (the steps before it carry the rounding of unordered float atomics through spike flips
+    into a trajectory of their own).  A few copies and fills on the current stream, no synchronisation."""
+    opt.flat_param.copy_(params0)
+    opt.m.zero_()
+    opt.v.zero_()
+    opt.norm_ws.zero_()
+    opt.steps = 0
+    leaves = []
+    _tensor_leaves(states, "", leaves)
+    for _name, t in leaves:
+        t.zero_()
+    from event_flow_amd.models import hip_ops
+
+    opt.step_invalidate()  # packed weights follow the parameters as after FlatAdam.step(): the fused engine re-packs at its next
+    hip_ops.repack_all()   # forward, the general path's cached operands are re-packed here, in place
+
+
+def collective_info(dp, opt, reduce_ms, one_graph, graphed):
+    """config.collective of the result line: what moves the gradient between the ranks (one rank: nothing does)."""
+    if not dp.active:
+        return {"backend": dp.backend, "library": ("RCCL " + ".".join(str(v) for v in torch.cuda.nccl.version())
+                                                   if torch.distributed.is_nccl_available() else None),
+                "ranks": 1, "per_step": "none at one rank (the all-reduce of [flat gradient | loss | new_seq] = "
+                                        "%d bytes is issued from 2 ranks on)" % (opt.comm.numel() * 4)}
+    return {"backend": dp.backend, "library": "RCCL " + ".".join(str(v) for v in torch.cuda.nccl.version())
+            if dp.backend == "nccl" else dp.backend,
+            "ranks": torch.distributed.get_world_size() if torch.distributed.is_initialized() else dp.world,
+            "per_step": "1 SUM all-reduce of [flat gradient | loss | new_seq] = %d bytes" % (opt.comm.numel() * 4),
+            # the collective's own device time (HIP events on its stream around every all-reduce of
+            # the timed region, this rank): what a scaling run has to compare its step time with
+            "all_reduce_us": ({"mean": float(np.mean(reduce_ms) * 1e3), "max": float(np.max(reduce_ms) * 1e3),
+                               "n": len(reduce_ms)} if reduce_ms else None),
+            "mode": ("captured: evf_allreduce_sum (ncclAllReduce on the library's own RCCL communicator) is a node "
+                     "of the step's ONE hipGraph" if one_graph else
+                     ("evf_allreduce_sum, eager" if dp.capturable else "torch.distributed all_reduce, eager")
+                     + (" between the step's two hipGraphs" if graphed else "")),
+            # the library's own communicator (EVF_DP_NATIVE=1, opt-in): asked for / why not used / the
+            # ranks RCCL itself counts on it (ncclCommCount) / RCCL's version code as that binding sees it
+            "native_requested": bool(getattr(dp, "native_requested", False)),
+            "native_fallback": getattr(dp, "native_fallback", None),
+            "native_comm_count": getattr(dp, "native_ranks", None),
+            "native_rccl_version": getattr(dp, "native_version", None),
+            "forced_at_one_rank": dp.world == 1}
+
+
+def conv_precision_text(precision):
+    return ("fp32 results via exact 3-way bf16 splits of the fp32 operands on the bf16 matrix cores, fp32 accumulation"
+            if precision == "bf16x3" else "fp32 MFMA (v_mfma_f32_32x32x2_f32)")
+
+
 def launch_floor_us():
     """Duration of a launch that does nothing worth mentioning (a 64-element add), from the two-point calibration every
     profile_start / profile_stop pair runs (T1 = o + t, T2 = o + 2t): the floor any single-kernel operator sits on."""
@@ -444,7 +545,7 @@ def other_config_line(cfg, steps=10, warmup=3, timeout=420, extra=None):
     (own model, own HIP context), summarised for the headline line: value, ms_per_step and the roofline object of that run."""
     import subprocess
 
-    cmd = [sys.executable, os.path.abspath(__file__)] + (["--config", cfg] if cfg else []) + ["--steps", str(steps), "--warmup", str(warmup),
+    cmd = [sys.executable, os.path.abspath(__file__)] + (["--config", cfg] if cfg else []) + ["--full", "--steps", str(steps), "--warmup", str(warmup),
            "--no-cpu-baseline", "--no-iwe", "--no-others"] + (["--no-graph-profile", "--repeat-blocks", "3"] + list(extra) if extra else [])
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
@@ -612,6 +713,7 @@ def main_c4(args):
     use_graph = not args.no_graph
     opt = FlatAdam(model, lr=2e-4, clip=100.0, device_step=use_graph)
     opt.zero_grad()
+    params0 = opt.flat_param.clone() if args.dump_outputs else None  # (rewind_to_start)
     pool = [encode_passes([torch.from_numpy(synthetic.event_list_batch(Bc, nev, Hc, Wc, synthetic.seed_for(4, 0, 0) + 100000 * w)).to(dev)],
                           2, (Hc, Wc)) for w in range(2)]
     side = torch.cuda.Stream()
@@ -643,8 +745,17 @@ def main_c4(args):
             print(f"[bench c4] hipGraph capture failed ({type(e).__name__}: {e}); running eager", file=sys.stderr)
             graphs = None
             torch.cuda.synchronize()
+    # --dump-outputs: the written step starts from the run's initial training state.  Only the first graph of the cycle reads
+    # state tensors Python holds (the second reads what the first wrote): the rewind goes before the last replay of graph 0
+    rewind_at = args.steps - 1
+    if graphs is not None and rewind_at % 2 == 1:
+        rewind_at -= 1
     t0 = time.perf_counter()
     for i in range(args.steps):
+        if params0 is not None and i == rewind_at:
+            from event_flow_amd.train import _general_states
+
+            rewind_to_start(opt, params0, _general_states(model)[1])
         if graphs is not None:
             graphs[i % 2][0].replay()
             loss = graphs[i % 2][1]
@@ -652,6 +763,28 @@ def main_c4(args):
             loss = train_window(model, lossf, opt, pool[i % 2])
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    c4_metric = "event-windows/sec (train step, 256x256x50k ev, LIF-EV-FlowNet)"
+    c4_workload = ("LIF-EV-FlowNet (SpikingRecEVFlowNet, base 32) full train step, 256x256, 50k events/window, batch 8, "
+                   "4 flow scales, CM loss, clip+Adam [BASELINE configs[3]]")
+    dumped = None
+    if args.dump_outputs:
+        # what the last timed step left to its caller: the loss it returned, the parameters and Adam moments after its update, the
+        # squared norm of its gradient before clipping (the 410 MB of recurrent state stay where the window graphs route them)
+        if graphs is not None:
+            loss = graphs[(args.steps - 1) % 2][1]
+        dumped = dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "params": opt.flat_param, "adam_m": opt.m, "adam_v": opt.v,
+                                                  "grad_sqnorm": opt.norm_ws[:1]})
+    if not args.full:
+        # the plain run: the headline figure and what describes it, nothing else measured
+        print(json.dumps({
+            "metric": c4_metric, "value": Bc * args.steps / elapsed, "unit": "event-windows/s", "n_gpus": 1, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": c4_workload, "baseline_config": "c4", "global_batch": Bc, "events_per_window": nev,
+                       "parallelism": "dp1", "launch": mode, "loss": float(loss), "state_tensors_copied_per_cycle": state_copies},
+            "workload_activity": {"thresh_scale": args.thresh_scale, "events": "uniform"}, "full": False, "dumped_outputs": dumped}),
+            flush=True)
+        return
     block_ms = [elapsed / args.steps * 1e3]  # (the contract's block, then the same region repeated: median and spread)
     if graphs is not None:
         for _ in range(max(args.repeat_blocks, 1) - 1):
@@ -700,11 +833,10 @@ def main_c4(args):
     dom = kernels[dom_name]
     c4_traffic, c4_traffic_why = _pmc_c4(dom_name)
     out = {
-        "metric": "event-windows/sec (train step, 256x256x50k ev, LIF-EV-FlowNet)", "value": Bc * args.steps / elapsed,
+        "metric": c4_metric, "value": Bc * args.steps / elapsed,
         "unit": "event-windows/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "LIF-EV-FlowNet (SpikingRecEVFlowNet, base 32) full train step, 256x256, 50k events/window, batch 8, "
-                               "4 flow scales, CM loss, clip+Adam [BASELINE configs[3]]", "baseline_config": "c4", "global_batch": Bc,
+        "config": {"workload": c4_workload, "baseline_config": "c4", "global_batch": Bc,
                    "events_per_window": nev, "parallelism": "dp1", "launch": mode, "loss": float(loss),
                    "state_tensors_copied_per_cycle": state_copies,
                    "conv_precision": ("forward / input gradient: bf16 MFMA with exact 3-way operand splits, fp32 accumulation "
@@ -734,7 +866,7 @@ def main_c4(args):
         "timing_blocks": {"ms_per_step": [round(v, 4) for v in block_ms], "steps_per_block": args.steps,
                           "median_ms_per_step": float(np.median(block_ms)),
                           "spread_pct": float(100.0 * (np.max(block_ms) - np.min(block_ms)) / np.median(block_ms))},
-        "workload_activity": {"thresh_scale": args.thresh_scale, "events": "uniform"},
+        "workload_activity": {"thresh_scale": args.thresh_scale, "events": "uniform"}, "full": True, "dumped_outputs": dumped,
         "kernels": kernels,
         "kernel_timing": {"method": "HIP events around each launch over eager steps, bracket overhead removed",
                           "bracket_overhead_us": round(_lib.last_event_overhead_ms * 1e3, 2)},
@@ -747,6 +879,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the line can hold: repeated timing blocks, per-kernel and "
+                         "roofline figures, the IWE sweep, the CPU baseline, the other configurations / workloads (the --no-* flags "
+                         "below switch parts of it off); without it the run only times its steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (loss, parameters, Adam moments, squared "
+                         "gradient norm, recurrent state; large tensors as a fixed, seeded sample) as DIR/<name>.npy.  The last timed "
+                         "step then starts from the initial parameters, zero Adam moments and a zero recurrent state (c4 with an odd "
+                         "last step index: the step before it), so that two runs write the same values up to rounding")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-iwe", action="store_true")
     ap.add_argument("--precision", choices=["bf16x3", "fp32"], default="bf16x3",
@@ -860,6 +1001,7 @@ def main():
     use_graph = not args.no_graph
     opt = FlatAdam(model, lr=2e-4, clip=100.0, device_step=use_graph)
     opt.zero_grad()
+    params0 = opt.flat_param.clone() if args.dump_outputs else None  # (rewind_to_start)
     # micro-batch pipelining (train.StreamReplicas): the rank's batch as `--streams` slices, each through its own replica
     # (shared weights, own state / tape / gradient buffer) on its own HIP stream; gradients summed before the one step
     nstream = args.streams if (args.streams > 1 and B_PER_GPU % args.streams == 0) else 1
@@ -922,7 +1064,7 @@ def main():
 
     dp.barrier()
     torch.cuda.synchronize()
-    if graphs is None:
+    if graphs is None and args.full:
         _lib.profile_start(names)
         _lib.load().evf_defer_profile(1)
     if dp.active:
@@ -930,6 +1072,10 @@ def main():
     t0 = time.perf_counter()
     loss = None
     for i in range(args.steps):
+        if params0 is not None and i == args.steps - 1:
+            # the step whose outputs are written starts from the run's initial training state (every rank alike)
+            rewind_to_start(opt, params0, graphs[(i - 1) % len(graphs)].left if graphs is not None else (
+                model.state_buffers() if reps is None else [m.state_buffers() for m in reps.models]))
         if graphs is not None:
             loss = graphs[i % len(graphs)].replay()
         else:
@@ -940,6 +1086,39 @@ def main():
     reduce_ms = dp.reduce_times_ms() if dp.active else []
     if dp.active:
         dp.time_reduces(False)
+    dumped = None
+    if args.dump_outputs and dp.rank == 0:
+        # what the last timed step left to its caller, before anything else runs: the loss it returned, the parameters and Adam
+        # moments after its update, the squared norm of its gradient before clipping, the recurrent state it handed on
+        last = graphs[(args.steps - 1) % len(graphs)].left if graphs is not None else (
+            model.state_buffers() if reps is None else [m.state_buffers() for m in reps.models])
+        dumped = dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "params": opt.flat_param, "adam_m": opt.m, "adam_v": opt.v,
+                                                  "grad_sqnorm": opt.norm_ws[:1], "state": last})
+    if not args.full:
+        # the plain run: the headline figure and what describes it, nothing else measured
+        elapsed = dp.max_over_ranks(elapsed)
+        loss_val = float(loss)
+        if dp.rank == 0:
+            one_graph = bool(dp.active and graphs is not None and graphs[0].post is None)
+            out = {
+                "metric": f"event-windows/sec (train step, {W}x{H}x{PASSES * EV_PER_PASS // 1000}k ev)" + ("" if args.config == "c3" else f" [{wl['model']}, {args.config}]"),
+                "value": B_PER_GPU * dp.world * args.steps / elapsed,
+                "unit": "event-windows/s", "n_gpus": dp.world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                "dtype": "f32", "data": "synthetic",
+                "config": {"workload": wl["text"], "baseline_config": args.config,
+                           "global_batch": B_PER_GPU * dp.world, "events_per_window": PASSES * EV_PER_PASS,
+                           "parallelism": f"dp{dp.world}", "launch": mode, "loss": loss_val, "streams": nstream,
+                           "collective": collective_info(dp, opt, reduce_ms, one_graph, graphs is not None),
+                           "conv_precision": conv_precision_text(model.precision)},
+                "workload_activity": {"thresh_scale": args.thresh_scale, "events": args.events},
+                "full": False, "dumped_outputs": dumped,
+            }
+            out["collective"] = out["config"]["collective"]
+            print(json.dumps(out), flush=True)
+        dp.barrier()
+        dp.close()
+        return
     # Spread of the headline figure: the SAME timed region (barrier, K replays, synchronize, barrier) four more times, right
     # after the contract's own block.  `value` / `ms_per_step` stay the first block's (the contract: exactly K steps); the
     # blocks, their median and their spread are reported beside them (every rank runs the same number of replays).
@@ -1351,32 +1530,8 @@ def main():
                                       "streams (replicas sharing the weights; gradients summed before the one optimizer step): "
                                       "kernels[*] / roofline are per LAUNCH of a micro-batch, timed one at a time; in the replayed "
                                       "step two such launches are in flight" if nstream > 1 else None),
-                       "collective": ({"backend": dp.backend, "library": "RCCL " + ".".join(str(v) for v in torch.cuda.nccl.version())
-                                       if dp.backend == "nccl" else dp.backend,
-                                       "ranks": torch.distributed.get_world_size() if torch.distributed.is_initialized() else dp.world,
-                                       "per_step": "1 SUM all-reduce of [flat gradient | loss | new_seq] = %d bytes" % (opt.comm.numel() * 4),
-                                       # the collective's own device time (HIP events on its stream around every all-reduce of
-                                       # the timed region, this rank): what a scaling run has to compare its step time with
-                                       "all_reduce_us": ({"mean": float(np.mean(reduce_ms) * 1e3), "max": float(np.max(reduce_ms) * 1e3),
-                                                          "n": len(reduce_ms)} if reduce_ms else None),
-                                       "mode": ("captured: evf_allreduce_sum (ncclAllReduce on the library's own RCCL communicator) is a node "
-                                                "of the step's ONE hipGraph" if one_graph else
-                                                ("evf_allreduce_sum, eager" if dp.capturable else "torch.distributed all_reduce, eager")
-                                                + (" between the step's two hipGraphs" if graphs is not None else "")),
-                                       # the library's own communicator (EVF_DP_NATIVE=1, opt-in): asked for / why not used / the
-                                       # ranks RCCL itself counts on it (ncclCommCount) / RCCL's version code as that binding sees it
-                                       "native_requested": bool(getattr(dp, "native_requested", False)),
-                                       "native_fallback": getattr(dp, "native_fallback", None),
-                                       "native_comm_count": getattr(dp, "native_ranks", None),
-                                       "native_rccl_version": getattr(dp, "native_version", None),
-                                       "forced_at_one_rank": dp.world == 1}
-                                      if dp.active else
-                                      {"backend": dp.backend, "library": ("RCCL " + ".".join(str(v) for v in torch.cuda.nccl.version())
-                                                                          if torch.distributed.is_nccl_available() else None),
-                                       "ranks": 1, "per_step": "none at one rank (the all-reduce of [flat gradient | loss | new_seq] = "
-                                                               "%d bytes is issued from 2 ranks on)" % (opt.comm.numel() * 4)}),
-                       "conv_precision": ("fp32 results via exact 3-way bf16 splits of the fp32 operands on the bf16 matrix cores, "
-                                          "fp32 accumulation" if model_precision == "bf16x3" else "fp32 MFMA (v_mfma_f32_32x32x2_f32)")},
+                       "collective": collective_info(dp, opt, reduce_ms, one_graph, graphs is not None),
+                       "conv_precision": conv_precision_text(model_precision)},
             "roofline": roof,
             "mfma_stack": {"mfma_busy_stack_pct": mfma_busy_stack, "kernels": stack, "kernels_without_pmc": stack_missing,
                            "issued_bf16_frac_of_peak_whole_step": issued_flop_step / (elapsed / args.steps) / 1e12 / BF16_MFMA_PEAK,
@@ -1391,6 +1546,7 @@ def main():
                               "spread_pct": float(100.0 * (np.max(block_ms) - np.min(block_ms)) / np.median(block_ms)),
                               "windows_per_s_median": B_PER_GPU * dp.world / (float(np.median(block_ms)) * 1e-3)},
             "workload_activity": {"thresh_scale": args.thresh_scale, "events": args.events},
+            "full": True, "dumped_outputs": dumped,
             "kernels": kernels, "entry_points_that_only_record": recorded_only,
             "kernel_timing": {"method": "diagonal / head-window launches: HIP events captured into an instrumented copy of the step graphs "
                                         "(timestamp-kernel nodes), read after its replays, minus the empty bracket of the same graph; "
@@ -1446,7 +1602,7 @@ def main():
             # c3 line has been measured (this process only waits meanwhile)
             torch.cuda.synchronize()
             out.setdefault("other_configs", {}).update({"c4": other_config_line("c4"), "c5": other_config_line("c5"),
-                                    "note": "`python bench.py --config c4|c5 --steps 10 --warmup 3`, one process each, run after the c3 "
+                                    "note": "`python bench.py --full --config c4|c5 --steps 10 --warmup 3`, one process each, run after the c3 "
                                             "line's timed region and side measurements; full lines: profiles/"})
         if dp.world == 1 and args.config == "c3" and not args.no_others and not args.no_alive and args.thresh_scale == 1.0:
             # The same step on an ALIVE network (thresholds x 0.25, moving-dots events: every layer at 20-50 % spike rate; parity of
@@ -1459,7 +1615,7 @@ def main():
                                ("c4_thresh_x0.25", ["--config", "c4", "--thresh-scale", "0.25"])):
                 alive[tag] = other_config_line(None, steps=20 if "c4" not in tag else 10, extra=extra)
             out["alive_workloads"] = {**alive, "default_ms_per_step": out["ms_per_step"],
-                                      "note": "`python bench.py <flags> --no-cpu-baseline --no-iwe --no-others`, one process each, after the "
+                                      "note": "`python bench.py --full <flags> --no-cpu-baseline --no-iwe --no-others`, one process each, after the "
                                               "headline line's measurements: the replayed step at another spike activity"}
             for tag, ent in alive.items():
                 out["config"]["alive_" + tag.replace(".", "") + "_ms_per_step"] = round(ent["ms_per_step"], 3) if "ms_per_step" in ent else None

@@ -168,7 +168,7 @@ def _bench_rccl_one_rank(extra, port, **more_env):
         env.pop(k, None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-                          "--no-cpu-baseline", "--no-iwe", "--no-others"] + extra,
+                          "--full", "--no-cpu-baseline", "--no-iwe", "--no-others"] + extra,
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, "\n".join(ln for ln in out.stderr.splitlines() if "frame #" not in ln)[-6000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

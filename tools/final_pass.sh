@@ -10,4 +10,5 @@ python tools/prof_summary.py $R > gpurun_out/final_$R/prof_summary.log 2>&1   # 
 bash tools/parity_report.sh gpurun_out/final_$R/parity_report.txt > /dev/null 2>&1
 tail -2 gpurun_out/final_$R/parity_report.txt
 cp gpurun_out/final_$R/parity_report.txt profiles/${R}_parity_report.txt   # (so that the bench line below sees the report of THESE sources)
-timeout 700 python bench.py > gpurun_out/final_$R/bench_default.json 2> gpurun_out/final_$R/bench_default.err; echo "bench rc=$?"
+D=$(dirname "$(ls */final_$R/parity_report.txt | head -1)")   # (this pass's output folder)
+timeout 700 python bench.py --full > $D/bench_default.json 2> $D/bench_default.err; echo "bench rc=$?"
