@@ -20,13 +20,26 @@ from .base import BaseModel
 from .engine import FireNetEngine
 
 
-def _xlif_fused_ok(c):
+def _xlif_fused_why(cells, precision):
     """XLIF and ALIF cells ride on the PLIF kernels (threshold t0 + t1 * trace instead of the trace in the current; ALIF: the trace
     driven by the cell's own previous spikes); their backward forms exist for the default neuron only (configs/train_SNN.yml: hard
-    reset, arctan surrogate) -- other XLIF / ALIF cells: general path (EVF_XLIF_FUSED=0: always)."""
-    import os
+    reset, arctan surrogate), with the trace backward inside the fused backward kernels, a two-channel input and the bf16x3 forward.
+    -> "" when the fused engine serves these cells, else the reason the general path does (EVF_XLIF_FUSED=0: always)."""
+    from . import engine
 
-    return bool(c.hard_reset) and c.activation == "arctanspike" and os.environ.get("EVF_XLIF_FUSED", "1") != "0"
+    if os.environ.get("EVF_XLIF_FUSED", "1") == "0":
+        return "EVF_XLIF_FUSED=0"
+    if not all(c.hard_reset and c.activation == "arctanspike" for c in cells):
+        return "XLIF / ALIF cells with the soft reset or another surrogate than arctanspike (their fused kernels: hard reset, arctan)"
+    if cells[0].input_size != 2:
+        return f"XLIF / ALIF cells behind a {cells[0].input_size}-channel input (their fused head kernels: two channels)"
+    if not engine.PLIF_TRACE_FUSED:
+        return "XLIF / ALIF cells with EVF_PLIF_TRACE_FUSED=0 (their trace backward exists inside the fused backward kernels only)"
+    if not engine.PLIF_BOX_IN_DGRAD:
+        return "XLIF / ALIF cells with EVF_PLIF_BOX=kernel (their trace backward needs the pooling adjoint inside the input-gradient kernels)"
+    if precision != "bf16x3":
+        return f"XLIF / ALIF cells with precision={precision!r} (their fused kernels: bf16x3)"
+    return ""
 from . import hip_ops
 from .model_util import CropParameters, copy_states
 from .unet import (
@@ -93,16 +106,16 @@ class FireNet(BaseModel):
 
     def _fused(self):
         """True when the network runs on the fused 32->32 spike kernels of models/engine.py (LIF / PLIF
-        FireNets at the reference's width); every other variant -- ANN FireNet (ConvLayer_/ConvGRU), ALIF/XLIF,
-        other widths, residual -- is chained cell by cell through the general path (models/hip_ops.py)."""
+        FireNets at the reference's width, and the XLIF / ALIF ones _xlif_fused_why admits); every other variant -- ANN FireNet
+        (ConvLayer_/ConvGRU), other widths, residual -- is chained cell by cell through the general path (models/hip_ops.py)."""
         if self._use_fused is None:
             cells = self._cells()
             self._use_fused = (
                 not self.residual
                 and all(getattr(c, "kind", None) in ("lif", "plif", "xlif", "alif") and not getattr(c, "wnorm", False) and not getattr(c, "gnorm", False)
                         for c in cells)
-                and all(c.kind not in ("xlif", "alif") or _xlif_fused_ok(c) for c in cells)
                 and len({c.kind for c in cells}) == 1
+                and not (cells[0].kind in ("xlif", "alif") and _xlif_fused_why(cells, self.precision))
                 and all(c.hidden_size == 32 and c.kernel_size == 3 and c.stride == 1 for c in cells)
             )
             if not self._use_fused and os.environ.get("EVF_PATH_NOTICE", "1") != "0":
@@ -111,7 +124,7 @@ class FireNet(BaseModel):
 
                 print(f"[event_flow_amd] {type(self).__name__}: general path (one fused conv + neuron kernel per cell, "
                       f"models/hip_ops.py) -- {self.compute_path[1]}; the recorded 32-channel window kernels (models/engine.py) "
-                      "serve LIF / PLIF FireNets (and XLIF / ALIF ones with the hard reset and the arctan surrogate) with base_num_channels=32, "
+                      "serve LIF / PLIF FireNets (and XLIF / ALIF ones with the hard reset, the arctan surrogate and a two-channel input) with base_num_channels=32, "
                       "kernel_size=3, no residual / weight / group norm",
                       file=sys.stderr)
         return self._use_fused
@@ -126,13 +139,10 @@ class FireNet(BaseModel):
             why.append("residual connections")
         if any(getattr(c, "kind", None) not in ("lif", "plif", "xlif", "alif") for c in cells):
             why.append("cell kind(s) " + ", ".join(sorted(str(k) for k in kinds)))
-        elif any(c.kind in ("xlif", "alif") and not _xlif_fused_ok(c) for c in cells):
-            import os
-
-            why.append("EVF_XLIF_FUSED=0" if os.environ.get("EVF_XLIF_FUSED", "1") == "0" else
-                       "XLIF / ALIF cells with the soft reset or another surrogate than arctanspike (their fused kernels: hard reset, arctan)")
         elif len(kinds) > 1:
             why.append("mixed cell kinds")
+        elif cells[0].kind in ("xlif", "alif") and _xlif_fused_why(cells, self.precision):
+            why.append(_xlif_fused_why(cells, self.precision))
         if any(getattr(c, "wnorm", False) or getattr(c, "gnorm", False) for c in cells):
             why.append("normalised weights / group norm")
         if any(getattr(c, "hidden_size", 32) != 32 or getattr(c, "kernel_size", 3) != 3 or getattr(c, "stride", 1) != 1 for c in cells):

@@ -23,7 +23,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from event_flow_amd import _lib  # noqa: E402
-from event_flow_amd.models.model import LIFFireNet, PLIFFireNet  # noqa: E402
+from event_flow_amd.models.model import ALIFFireNet, LIFFireNet, PLIFFireNet, XLIFFireNet  # noqa: E402
 from event_flow_amd.train import FlatAdam, encode_passes  # noqa: E402
 from oracle import loss as oloss  # noqa: E402
 from oracle import snn as osnn  # noqa: E402
@@ -38,13 +38,16 @@ def N(t):
     return t.detach().cpu().numpy()
 
 
-def _oracle_window(name, params, keys, passes, res, lcfg):
+NEURON_KINDS = {"LIFFireNet": "lif", "PLIFFireNet": "plif", "XLIFFireNet": "xlif", "ALIFFireNet": "alif"}
+
+
+def _oracle_window(name, params, keys, passes, res, lcfg, hard_reset=None):
     """The oracle's window with everything kept: states[t][l] = (v', z'[, pt']), flows[t], loss, dL/dparams, dL/dflow[t]."""
     leaves = {k: t.detach().clone().requires_grad_(k in keys) for k, t in params.items()}
     win = oloss.Window(res)
     states, flows, per_pass = [None] * 7, [], []
     for d in passes:
-        flow, states = osnn.firenet_forward(name, leaves, d["event_cnt"], states)
+        flow, states = osnn.firenet_forward(name, leaves, d["event_cnt"], states, hard_reset=hard_reset)
         win.add([flow], d["event_list"], d["event_list_pol_mask"], d["event_mask"])
         flows.append(flow)
         per_pass.append(states)
@@ -76,19 +79,23 @@ def _read_state(eng, hip):
 def _teacher_forced(cls, name, cfg, H, W, B, P, n_ev, thresh_scale, kind, seed):
     from event_flow_amd import synthetic
 
-    plif = name == "PLIFFireNet"
+    nk = NEURON_KINDS[name]
+    plif = nk in ("plif", "xlif", "alif")  # three state tensors: the PLIF entry points, the neuron kind in bits 1-2 of their reset flag
+    adaptive = nk in ("xlif", "alif")  # threshold t0 + t1 * trace'; t0 / t1 are parameters (learn_thresh) in the `thresh` / `add_pt` slots
     torch.manual_seed(seed)
     model = cls(dict(cfg)).to(DEV)
     model.precision = "bf16x3"
     with torch.no_grad():
         for k, p in model.named_parameters():
-            if k.endswith("thresh"):
+            if k.endswith(".t0" if adaptive else "thresh"):
                 p.mul_(thresh_scale)
     model.train()
     opt = FlatAdam(model, lr=2e-4, clip=100.0)
     opt.zero_grad()
     params = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
-    keys = osnn.trainable_keys(params)
+    keys = osnn.trainable_keys(params, learn_thresh_t=adaptive)
+    if adaptive:
+        assert {f"{ln}.{q}" for ln in LAYERS for q in ("t0", "t1")} <= set(keys) & {k for k, p in model.named_parameters() if p.requires_grad}
     lists = []
     for k in range(P):
         ev = synthetic.event_list_batch(B, n_ev, H, W, 8100 + 100 * k, kind=kind)
@@ -98,8 +105,8 @@ def _teacher_forced(cls, name, cfg, H, W, B, P, n_ev, thresh_scale, kind, seed):
         d["event_voxel"] = None
     opasses = [{k: v.detach().cpu() for k, v in d.items() if v is not None} for d in passes]
     lcfg = {"flow_regul_weight": 0.001, "mask_output": True}
-    torch.set_num_threads(32)
-    ora = _oracle_window(name, params, keys, opasses, (H, W), lcfg)
+    torch.set_num_threads(16 if adaptive else 32)
+    ora = _oracle_window(name, params, keys, opasses, (H, W), lcfg, hard_reset=True if adaptive else None)
     rates = [float(st[1].mean()) for st in ora["states"][-1]]
     print(f"[teacher-forced {name} x{thresh_scale} {kind}] oracle spike rate per layer (last pass): {[f'{r:.4f}' for r in rates]}, "
           f"loss {ora['loss']:.6f}")
@@ -108,7 +115,14 @@ def _teacher_forced(cls, name, cfg, H, W, B, P, n_ev, thresh_scale, kind, seed):
     eng = model._eng()
     eng._prepare(torch.device(DEV))
     F, PK = eng._flat, eng._packed
-    hard = 1
+    if adaptive:  # the slots FireNetEngine.__init__ registers: `thresh` is t0, `add_pt` is t1, `leak_pt` the trace's leak (leak_t of an ALIF cell)
+        cells = dict(zip(LAYERS, eng.cells))
+        slot = dict(zip(eng.pnames, eng.params))
+        for i, ln in enumerate(LAYERS):
+            assert slot[f"{i}.thresh"] is cells[ln].t0 and slot[f"{i}.add_pt"] is cells[ln].t1
+            assert slot[f"{i}.leak_pt"] is (cells[ln].leak_pt if nk == "xlif" else cells[ln].leak_t)
+        assert eng._xf == {"xlif": 2, "alif": 4}[nk]
+    hard = 1 | {"xlif": 2, "alif": 4}.get(nk, 0)  # (include/evflow.h: bits 1-2 of the PLIF entry points' reset flag)
     L = _lib.load()
 
     # ---------------- forward, cell by cell on the oracle's inputs; the hidden cells of a pass as ONE recorded diagonal launch
@@ -172,7 +186,11 @@ def _teacher_forced(cls, name, cfg, H, W, B, P, n_ev, thresh_scale, kind, seed):
         for i in range(7):
             vo, zo = N(ost[i][0]), N(ost[i][1])
             vh, zh = got[i][0], got[i][1]
-            th = np.maximum(N(params[f"{LAYERS[i]}.thresh"]).reshape(1, -1, 1, 1), 0.01)
+            if adaptive:  # per element: t0 + t1 * trace' of the ORACLE
+                th = (np.maximum(N(params[f"{LAYERS[i]}.t0"]).reshape(1, -1, 1, 1), 0.01)
+                      + np.maximum(N(params[f"{LAYERS[i]}.t1"]).reshape(1, -1, 1, 1), 0.0) * N(ost[i][2]))
+            else:
+                th = np.maximum(N(params[f"{LAYERS[i]}.thresh"]).reshape(1, -1, 1, 1), 0.01)
             scale = max(float(np.abs(vo).max()), 1e-20)
             e_l2 = float(np.linalg.norm(vh - vo) / max(np.linalg.norm(vo), 1e-20))
             e_max = float(np.abs(vh - vo).max() / scale)
@@ -235,8 +253,10 @@ def _teacher_forced(cls, name, cfg, H, W, B, P, n_ev, thresh_scale, kind, seed):
                 tapes[t + 1]["layers"][i][6].copy_(src[i][2])
             if plif:
                 lay[8].copy_(src[i][3])
-                xin = opasses[t]["event_cnt"] if i == 0 else ora["states"][t][i - 1][1]
-                lay[9].copy_(osnn._pretrace(xin, 3, 1)[:, 0].to(DEV))  # pooled pre-synaptic activity of the ORACLE's input
+                if nk != "alif":  # (ALIF: the trace is driven by the cell's own previous spikes, loaded above; the backward puts its g_zx
+                    # buffer into the kernels' P slot, include/evflow.h -- the forward's P_out is read by nobody)
+                    xin = opasses[t]["event_cnt"] if i == 0 else ora["states"][t][i - 1][1]
+                    lay[9].copy_(osnn._pretrace(xin, 3, 1)[:, 0].to(DEV))  # pooled pre-synaptic activity of the ORACLE's input
         tapes[t]["flow"].data.copy_(ora["flows"][t].to(DEV))  # (the tape's flow map IS the node's output: .data has its own version counter)
         # aliasing the engine relies on (a pass's previous state IS the previous pass's output): checked, not assumed
         if t > 0:
@@ -299,6 +319,11 @@ PLIF_CFG = dict(LIF_CFG, name="PLIFFireNet",
                                 "learn_thresh": True, "hard_reset": True})
 
 
+ADAPTIVE_NEURON = {"leak_v": [-4.0, 0.1], "t0": [0.3, 0.05], "t1": [0.5, 0.1], "learn_leak": True, "learn_thresh": True, "hard_reset": True}
+XLIF_CFG = dict(LIF_CFG, name="XLIFFireNet", spiking_neuron=dict(ADAPTIVE_NEURON, leak_pt=[-2.0, 0.1]))
+ALIF_CFG = dict(LIF_CFG, name="ALIFFireNet", spiking_neuron=dict(ADAPTIVE_NEURON, leak_t=[-2.0, 0.1]))
+
+
 @pytest.mark.parametrize("thresh_scale,kind", [(0.25, "uniform"), (0.5, "moving_dots")])
 def test_teacher_forced_c3_lif_firenet_alive_at_benched_size(thresh_scale, kind):
     """BASELINE configs[2] per-GPU shard: B = 8, 128 x 128, 10 passes x 1500 events, thresholds x 0.25 (uniform events) and x 0.5
@@ -309,3 +334,19 @@ def test_teacher_forced_c3_lif_firenet_alive_at_benched_size(thresh_scale, kind)
 def test_teacher_forced_c5_plif_firenet_alive_at_per_gpu_batch():
     """BASELINE configs[4] per-GPU shard: PLIF-FireNet, 260 x 346, B = 4, 10 passes x 1500 events, thresholds x 0.25."""
     _teacher_forced(PLIFFireNet, "PLIFFireNet", PLIF_CFG, 260, 346, 4, 10, 1500, 0.25, "uniform", seed=1)
+
+
+def test_teacher_forced_c3_xlif_firenet_alive_at_benched_size():
+    """The shape bench.py's `firenet_family_at_c3_shape` times: XLIF-FireNet, B = 8, 128 x 128, 10 passes x 1500 events, the network as
+    initialised (t0 unscaled: every layer spikes by the reference arithmetic alone).  The PLIF entry points in their XLIF mode:
+    threshold t0 + t1 * trace' per element, t0 / t1 / both leaks among the gradients held to the harness's bars."""
+    r = _teacher_forced(XLIFFireNet, "XLIFFireNet", XLIF_CFG, 128, 128, 8, 10, 1500, 1.0, "uniform", seed=0)
+    assert r["rates"] and min(r["rates"][:5]) > 1e-3
+
+
+def test_teacher_forced_c3_alif_firenet_alive_at_benched_size():
+    """... and ALIF-FireNet: the threshold trace integrates the cell's own, un-detached, previous spikes, so every pass sends
+    (1 - s(leak_t)) * dL/d(trace') into dL/d(spikes) of the pass before (g_zx) -- a chain across all 10 passes that only a window of
+    an alive network exercises; a missing or doubled term shows in the gradients here."""
+    r = _teacher_forced(ALIFFireNet, "ALIFFireNet", ALIF_CFG, 128, 128, 8, 10, 1500, 1.0, "uniform", seed=0)
+    assert r["rates"] and min(r["rates"][:5]) > 1e-3

@@ -3,6 +3,10 @@ window kernels: the PLIF kernels with the pre-synaptic trace in the THRESHOLD (t
 (include/evflow.h: bit 1 of the PLIF entry points' reset / accumulate flag).  Against the CPU oracle (pinned by the single-cell
 goldens G6) and against the same network chained cell by cell on the general path."""
 
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -15,6 +19,7 @@ from event_flow_amd.loss import flow as hloss  # noqa: E402
 from event_flow_amd.models.model import ALIFFireNet, XLIFFireNet  # noqa: E402
 from event_flow_amd.train import FlatAdam, window_backward  # noqa: E402
 from oracle import snn as osnn  # noqa: E402
+from oracle.golden_parts import load_parts  # noqa: E402
 from oracle import train as otrain  # noqa: E402
 
 DEV = "cuda:0"
@@ -222,3 +227,254 @@ def test_xlif_alif_hipgraph_replay_is_bitwise_the_eager_step_under_a_determinist
         assert torch.equal(a, b)
     sd0 = make().state_dict()
     assert any(float((p.detach() - sd0[k].to(DEV)).abs().max()) > 0 for k, p in m1.named_parameters() if k.endswith(("t0", "t1")))  # (the adaptive threshold trained)
+
+
+# ------------------------------------------------------------------ the reference's own numbers (tests/golden/g7_{x,a}liffirenet_*)
+LAYERS = ["head", "G1", "R1a", "R1b", "G2", "R2a", "R2b"]
+# (fixture, network, path): hard-reset fixtures on the fused engine and -- EVF_XLIF_FUSED=0 -- on the general path; the soft-reset
+# ones (the reference constructors' default) on the general path, which is what serves them
+GOLDEN_FWD = [("g7_xliffirenet_train", "XLIFFireNet", "fused"), ("g7_aliffirenet_train", "ALIFFireNet", "fused"),
+              ("g7_xliffirenet_train", "XLIFFireNet", "general"), ("g7_aliffirenet_train", "ALIFFireNet", "general"),
+              ("g7_xliffirenet_soft", "XLIFFireNet", "soft"), ("g7_aliffirenet_soft", "ALIFFireNet", "soft")]
+GOLDEN_TRAIN = GOLDEN_FWD[:2] + [("g7_xliffirenet_train", "XLIFFireNet", "recorded"), ("g7_aliffirenet_train", "ALIFFireNet", "recorded")] + GOLDEN_FWD[2:]
+
+
+def G(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _golden_model(g, name, path, monkeypatch):
+    cls, neuron, _ = NETS[name]
+    hard = bool(g["meta_hard_reset"])
+    assert hard == (path != "soft")
+    monkeypatch.setenv("EVF_PATH_NOTICE", "0")
+    if path == "general":
+        monkeypatch.setenv("EVF_XLIF_FUSED", "0")
+    model = cls(cfg(dict(neuron, hard_reset=hard))).to(DEV)
+    missing, unexpected = model.load_state_dict({k[len("param0_"):]: torch.from_numpy(g[k]) for k in g.files if k.startswith("param0_")})
+    assert not missing and not unexpected  # the reference's state_dict keys load unchanged
+    assert model.compute_path[0] == ("fused" if path in ("fused", "recorded") else "general"), model.compute_path
+    assert model._fused() == (path in ("fused", "recorded"))
+    return model
+
+
+def _golden_passes(g):
+    keys = ("event_cnt", "event_voxel", "event_list", "event_list_pol_mask", "event_mask")
+    return [{k: G(g[f"p{i}_{k}"]) for k in keys} for i in range(int(g["meta_P"]))]
+
+
+def _golden_thresh(g, i, ln):
+    """The reference's per-element threshold of pass i, layer ln: t0.clamp_min(0.01) + t1.clamp_min(0) * trace'."""
+    return np.maximum(g[f"param0_{ln}.t0"], np.float32(0.01))[None] + np.maximum(g[f"param0_{ln}.t1"], np.float32(0))[None] * g[f"p{i}_aux_{ln}"]
+
+
+def _golden_forward(g, model, passes, tag):
+    """The passes under no_grad against the reference's per-layer numbers with the bars of tests/test_gpu_network.py::
+    test_forward_per_layer_and_flow: spikes equal wherever the reference's margin exceeds 1e-4; flips over ALL passes counted
+    (<= 1e-5 of the elements: 7 of 774 144); while no spike has flipped v' and the trace rtol 1e-5 / atol 2e-6, flow rtol 1e-4.
+    -> (flips, elements)."""
+    nflip = ntot = 0
+    worst_v = worst_t = worst_f = 0.0
+    with torch.no_grad():
+        for i, d in enumerate(passes):
+            out = model(d["event_voxel"], d["event_cnt"], log=True)
+            states = model.states
+            for li, ln in enumerate(LAYERS):
+                v_ref, z_ref, t_ref = g[f"p{i}_v_{ln}"], g[f"p{i}_z_{ln}"].astype(np.float32), g[f"p{i}_aux_{ln}"]
+                v, z, tr = N(states[li][0]), N(states[li][1]), N(states[li][2])
+                safe = np.abs(v_ref - _golden_thresh(g, i, ln)) > 1e-4
+                nflip += int((z != z_ref).sum())
+                ntot += z.size
+                assert np.array_equal(z[safe], z_ref[safe]), (i, ln, int((z != z_ref)[safe].sum()))
+                if nflip == 0:  # (a flipped borderline spike upstream legitimately changes everything downstream)
+                    worst_v = max(worst_v, float((np.abs(v - v_ref) / (2e-6 + 1e-5 * np.abs(v_ref))).max()))
+                    worst_t = max(worst_t, float((np.abs(tr - t_ref) / (2e-6 + 1e-5 * np.abs(t_ref))).max()))
+                    np.testing.assert_allclose(v, v_ref, rtol=1e-5, atol=2e-6, err_msg=f"{i} {ln}")
+                    np.testing.assert_allclose(tr, t_ref, rtol=1e-5, atol=2e-6, err_msg=f"{i} {ln} trace")
+            if nflip == 0:
+                f, f_ref = N(out["flow"][0]), g[f"p{i}_flow"]
+                worst_f = max(worst_f, float((np.abs(f - f_ref) / (1e-7 + 1e-4 * np.abs(f_ref))).max()))
+                np.testing.assert_allclose(f, f_ref, rtol=1e-4, atol=1e-7)
+            assert set(out["activity"].keys()) == {"0:input", "1:head", "2:G1", "3:R1a", "4:R1b", "5:G2", "6:R2a", "7:R2b", "8:pred"}
+    print(f"[{tag} forward] spike flips over all passes {nflip} of {ntot}; worst error as a fraction of its bar (while no spike had flipped): "
+          f"v' {worst_v:.3f}, trace {worst_t:.3f}, flow {worst_f:.3f}")
+    assert nflip <= 1e-5 * ntot, (nflip, ntot)
+    return nflip, ntot
+
+
+@pytest.mark.parametrize("fix,name,path", GOLDEN_FWD)
+def test_golden_forward_per_layer_and_flow(monkeypatch, fix, name, path):
+    """XLIF / ALIF FireNets against the REFERENCE's run (not the oracle's): per pass and layer the potential, the spikes and the
+    threshold trace, and the flow.  The fixtures' model seeds were chosen for the largest minimum margin |v' - thresh|
+    (6.6e-6 .. 1.4e-5, meta_min_margin), so a flip is possible and counted."""
+    g = load_parts(fix)
+    model = _golden_model(g, name, path, monkeypatch)
+    model.eval()
+    _golden_forward(g, model, _golden_passes(g), f"{fix} {path}")
+
+
+@pytest.mark.parametrize("fix,name,path", GOLDEN_TRAIN)
+def test_golden_train_step(monkeypatch, fix, name, path):
+    """One training window (3 passes, contrast loss, backward, clip + Adam) against the reference's loss, gradient norm, 39 gradient
+    tensors and updated parameters, with the bars tests/test_gpu_network.py::test_train_step_vs_golden holds LIF / PLIF to: loss
+    2e-5, grad_norm 2e-4, every tensor 2e-4 of its own norm + 1e-6 of the whole gradient when the census over all passes found no
+    spike flip (10x those when it did; at most 1e-5 of the spikes may flip).  `recorded`: FlatAdam + train.window_backward (the
+    window kernels, layer by layer); `fused`: plain autograd on the fused kernels, pass by pass; `general` / `soft`: cell by cell."""
+    g = load_parts(fix)
+    trace_leak = NETS[name][2]
+    gall = np.sqrt(sum(float((g[k].astype(np.float64) ** 2).sum()) for k in g.files if k.startswith("grad_") and k != "grad_norm"))
+    np.testing.assert_allclose(gall, float(g["grad_norm"]), rtol=1e-5)
+    for ln in LAYERS:  # the adaptive threshold's own parameters and both leaks carry signal in every layer: no bar below is vacuous
+        for q in ("t0", "t1", "leak_v", trace_leak):
+            # (more than the 1e-6 of the whole gradient every tensor's bar adds: a zero gradient would not pass for any of them)
+            assert np.linalg.norm(g[f"grad_{ln}.{q}"]) > 1e-6 * gall, (ln, q, np.linalg.norm(g[f"grad_{ln}.{q}"]), gall)
+    model = _golden_model(g, name, path, monkeypatch)
+    model.train()
+    passes = _golden_passes(g)
+    nflip, ntot = _golden_forward(g, model, passes, f"{fix} {path}")  # the census (all passes); asserts <= 1e-5 of the elements
+    model.reset_states()
+    H, W = passes[0]["event_cnt"].shape[2:]
+    lossf = hloss.EventWarping(loss_cfg(H, W), DEV)
+    if path == "recorded":
+        opt = FlatAdam(model, lr=2e-4, clip=100.0)
+        opt.zero_grad()
+        loss = window_backward(model, lossf, opt, passes)
+    else:
+        for d in passes:
+            out = model(d["event_voxel"], d["event_cnt"])
+            lossf.event_flow_association(out["flow"], d["event_list"], d["event_list_pol_mask"], d["event_mask"])
+        loss = lossf()
+        loss.backward()
+    last = sum(int((N(model.states[li][1]) != g[f"p{len(passes) - 1}_z_{ln}"].astype(np.float32)).sum()) for li, ln in enumerate(LAYERS))
+    assert last <= nflip, (last, nflip)  # (the window ran the spike trains the census saw)
+    grads = {k: N(p.grad).copy() for k, p in model.named_parameters()}
+    assert len(grads) == 39
+    if path == "recorded":
+        opt.step()
+        gn = opt.grad_norm()
+    else:
+        gn = float(torch.nn.utils.clip_grad_norm_(model.parameters(), 100.0))
+        torch.optim.Adam(model.parameters(), lr=2e-4).step()
+    newp = {k: N(v).copy() for k, v in model.state_dict().items()}
+    loss = float(loss.detach())
+    tight = nflip == 0
+    worst = ("", 0.0)
+    for k, got in grads.items():
+        ref = g["grad_" + k]
+        r = float(np.linalg.norm(got - ref) / max(np.linalg.norm(ref), 1e-6 * gall))
+        if r > worst[1]:
+            worst = (k, r)
+    e_all = np.sqrt(sum(float(((grads[k] - g["grad_" + k]).astype(np.float64) ** 2).sum()) for k in grads)) / gall
+    print(f"[{fix} {path} train] spike flips over all passes {nflip} of {ntot}; loss rel {abs(loss - float(g['loss'])) / abs(float(g['loss'])):.2e}, "
+          f"grad_norm rel {abs(gn - float(g['grad_norm'])) / float(g['grad_norm']):.2e}, whole gradient rel-L2 {e_all:.2e}, "
+          f"worst tensor {worst[0]} {worst[1]:.2e}; " + ", ".join(
+              f"{q} {max(float(np.linalg.norm(grads[f'{ln}.{q}'] - g[f'grad_{ln}.{q}']) / np.linalg.norm(g[f'grad_{ln}.{q}'])) for ln in LAYERS):.2e}"
+              for q in ("t0", "t1", "leak_v", trace_leak)))
+    np.testing.assert_allclose(loss, float(g["loss"]), rtol=2e-5 if tight else 2e-4)
+    np.testing.assert_allclose(gn, float(g["grad_norm"]), rtol=2e-4 if tight else 2e-3)
+    for k, got in grads.items():
+        ref = g["grad_" + k]
+        denom = max(np.linalg.norm(ref), 1e-12)
+        assert np.linalg.norm(got - ref) <= (2e-4 if tight else 2e-3) * denom + 1e-6 * gall, (k, np.linalg.norm(got - ref) / denom, nflip)
+    for k, ref in ((k[len("param1_"):], g[k]) for k in g.files if k.startswith("param1_")):
+        # the first Adam step moves every weight by ~lr*sign(g): weights whose gradient is at the fp32 noise floor may move the other
+        # way (<= 2*lr apart); the bulk must agree
+        d = np.abs(newp[k] - ref)
+        assert d.max() <= 2 * 2e-4 + 1e-6, k
+        assert np.mean(d > 2e-5) <= 0.02, (k, np.mean(d > 2e-5))
+
+
+# ------------------------------------------------------------------ configurations the fused engine does not serve: general path
+@pytest.mark.parametrize("name", ["XLIFFireNet", "ALIFFireNet"])
+def test_voxel_input_xlif_alif_firenets_run_on_the_general_path_vs_oracle(monkeypatch, name):
+    """`encoding: voxel, num_bins: 5` with the default (hard reset, arctan) XLIF / ALIF neuron: the fused engine's XLIF / ALIF head
+    kernels take a two-channel input only, so FireNet._fused() must send the network to the general path -- it used to report
+    compute_path == "fused" and raise EvflowError in its first backward.  Two passes, contrast loss, backward: flows, states and
+    every parameter gradient against the oracle with the bars of tests/test_gpu_general.py::test_adaptive_threshold_firenets_vs_oracle."""
+    monkeypatch.setenv("EVF_PATH_NOTICE", "0")
+    B, n, H, W, P = 2, 400, 16, 20, 2
+    cls, neuron, _ = NETS[name]
+    torch.manual_seed(5)
+    c = cfg(neuron)
+    c.update(encoding="voxel", num_bins=5)
+    model = cls(c).to(DEV)
+    assert model.compute_path[0] == "general" and "5-channel input" in model.compute_path[1], model.compute_path
+    assert not model._fused()
+    model.train()
+    passes = [encode_event_list(torch.from_numpy(synthetic.event_list_batch(B, n, H, W, 4100 + 10 * k)).to(DEV), 5, (H, W)) for k in range(P)]
+    assert tuple(passes[0]["event_voxel"].shape) == (B, 5, H, W)
+    lossf = hloss.EventWarping(loss_cfg(H, W), DEV)
+    flows = []
+    for d in passes:
+        out = model(d["event_voxel"], d["event_cnt"])
+        flows.append(out["flow"][0])
+        lossf.event_flow_association(out["flow"], d["event_list"], d["event_list_pol_mask"], d["event_mask"])
+    loss = lossf()
+    loss.backward()  # (raised EvflowError before)
+    params = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    keys = [k for k, _ in model.named_parameters()]
+    leaves = {k: t.requires_grad_(k in keys) for k, t in params.items()}
+    opasses = [{k: v.detach().cpu() for k, v in d.items()} for d in passes]
+    l_ref, f_ref, st_ref = otrain.forward_window(name, leaves, opasses, [None] * 7, (H, W), loss_cfg={"flow_regul_weight": 0.001, "mask_output": True},
+                                                 model_cfg={"hard_reset": True, "encoding": "voxel"})
+    g_ref = torch.autograd.grad(l_ref, [leaves[k] for k in keys], allow_unused=True)
+    for f, fr in zip(flows, f_ref):
+        np.testing.assert_allclose(N(f), fr[0].detach().numpy(), rtol=1e-4, atol=1e-7)
+    for li, st in enumerate(model.states):
+        np.testing.assert_allclose(N(st), torch.stack(st_ref[li]).detach().numpy(), rtol=1e-5, atol=2e-6)
+        assert float(st[1].detach().mean()) > 0.01, li  # (the layer spikes)
+    np.testing.assert_allclose(float(loss.detach()), float(l_ref.detach()), rtol=1e-4)
+    named = dict(model.named_parameters())
+    worst = ("", 0.0)
+    for k, ref in zip(keys, g_ref):
+        ref = ref.numpy() if ref is not None else np.zeros(tuple(named[k].shape), np.float32)
+        got = N(named[k].grad) if named[k].grad is not None else np.zeros_like(ref)
+        denom = max(np.linalg.norm(ref), 1e-12)
+        r = float(np.linalg.norm(got - ref) / denom)
+        worst = max(worst, (k, r), key=lambda kr: kr[1])
+        assert np.linalg.norm(got - ref) <= 2e-3 * denom + 1e-9, (k, r)
+    print(f"[{name} voxel x5, general path] loss {float(loss.detach()):.6f} vs oracle {float(l_ref.detach()):.6f}; worst gradient tensor {worst[0]} {worst[1]:.2e}")
+    assert float(np.abs(N(named["head.ff.weight"].grad)).max()) > 0 and tuple(named["head.ff.weight"].shape) == (32, 5, 3, 3)
+
+
+_CHILD = """
+import torch
+from event_flow_amd import synthetic
+from event_flow_amd.dataloader.encodings import encode_event_list
+from event_flow_amd.loss import flow as hloss
+from event_flow_amd.models import engine
+from event_flow_amd.models.model import XLIFFireNet
+from event_flow_amd.train import FlatAdam, train_window
+assert not engine.PLIF_TRACE_FUSED
+B, n, H, W, P = 2, 400, 16, 20, 2
+torch.manual_seed(5)
+model = XLIFFireNet({"num_bins": 2, "base_num_channels": 32, "kernel_size": 3, "encoding": "cnt", "norm_input": False, "mask_output": True,
+                     "activations": ["arctanspike", "arctanspike"],
+                     "spiking_neuron": {"leak_v": [-4.0, 0.1], "leak_pt": [-2.0, 0.1], "t0": [0.3, 0.05], "t1": [0.5, 0.1], "learn_leak": True,
+                                        "learn_thresh": True, "hard_reset": True}}).to("cuda:0")
+path = model.compute_path
+assert path[0] == "general" and "EVF_PLIF_TRACE_FUSED" in path[1], path
+assert not model._fused()
+model.train()
+before = {k: p.detach().clone() for k, p in model.named_parameters()}
+opt = FlatAdam(model, lr=2e-4, clip=100.0)
+opt.zero_grad()
+lossf = hloss.EventWarping({"loader": {"resolution": [H, W]}, "loss": {"flow_regul_weight": 0.001, "overwrite_intermediate": False},
+                            "model": {"mask_output": True}}, "cuda:0")
+passes = [encode_event_list(torch.from_numpy(synthetic.event_list_batch(B, n, H, W, 4100 + 10 * k)).to("cuda:0"), 2, (H, W)) for k in range(P)]
+loss = float(train_window(model, lossf, opt, passes))
+torch.cuda.synchronize()
+moved = sum(int((p.detach() != before[k]).any()) for k, p in model.named_parameters())
+assert loss == loss and moved == 39, (loss, moved)
+print("TRAINED-ON-THE-GENERAL-PATH", loss, moved)
+"""
+
+
+def test_xlif_firenet_without_the_fused_trace_backward_trains_on_the_general_path():
+    """EVF_PLIF_TRACE_FUSED=0 (read when models/engine.py is imported: a fresh child process): a default XLIF FireNet used to raise
+    NotImplementedError when its engine was built; it trains one window on the general path."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, EVF_PLIF_TRACE_FUSED="0", EVF_PATH_NOTICE="0", PYTHONPATH=root, PYTHONNOUSERSITE="1")
+    r = subprocess.run([sys.executable, "-c", _CHILD], env=env, cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "TRAINED-ON-THE-GENERAL-PATH" in r.stdout, r.stdout[-2000:]

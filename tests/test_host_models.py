@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from oracle.golden_parts import load_parts
 
 from event_flow_amd import _lib
 from event_flow_amd.models import model as M
@@ -48,6 +49,22 @@ def test_reference_state_dicts_load_unchanged():
     _load(M.LeakyRecEVFlowNet(cfg(C=4, neuron=leaky, acts=("relu", None))), g11, "LeakyRecEVFlowNet.param_")
     sd = _load(M.SpikingRecEVFlowNet(cfg(C=4)), load_golden("g9_spiking_unet"), "param_")
     assert sd["multires_unetrec.decoders.1.conv2d.ff.weight"].shape == (16, 66, 3, 3)  # cat(pred, x, skip)
+
+
+@pytest.mark.parametrize("fix,cls,trace_leak,hard", [("g7_xliffirenet_train", "XLIFFireNet", "leak_pt", True), ("g7_aliffirenet_train", "ALIFFireNet", "leak_t", True),
+                                                     ("g7_xliffirenet_soft", "XLIFFireNet", "leak_pt", False), ("g7_aliffirenet_soft", "ALIFFireNet", "leak_t", False)])
+def test_reference_adaptive_threshold_state_dicts_load_unchanged(fix, cls, trace_leak, hard):
+    """The reference's XLIF / ALIF FireNets with learnable t0 / t1 (fixtures stored in parts): 39 parameters, all loaded by name."""
+    neuron = {"leak_v": [-4.0, 0.1], trace_leak: [-2.0, 0.1], "t0": [0.3, 0.05], "t1": [0.5, 0.1], "learn_leak": True, "learn_thresh": True,
+              "hard_reset": hard}
+    model = getattr(M, cls)(cfg(neuron=neuron))
+    g = load_parts(fix)
+    assert bool(g["meta_hard_reset"]) == hard
+    sd = _load(model, g, "param0_")
+    named = dict(model.named_parameters())
+    assert len(named) == 39 and {"head.t0", "head.t1", "G1." + trace_leak, "R2b.leak_v"} <= set(named)
+    assert all(torch.equal(named[k].detach(), sd[k]) for k in named)
+    assert sorted(named) == sorted(k[len("grad_"):] for k in g.files if k.startswith("grad_") and k != "grad_norm")
 
 
 def test_parameter_counts_match_the_reference():
