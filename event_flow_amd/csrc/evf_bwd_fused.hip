@@ -38,6 +38,27 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define FB_NW (FB_CW / 32 + 2)  // plane words per (row, channel): segment + one halo word each side
 #define FB_R0 32768             // LDS region 0: operand double buffer (24 KiB), later the tap-8 reduction (32 KiB)
 
+// ---- the leak gradient without the previous potential (two-team bodies, one-pass cells: bits of the `accumulate` word) ----
+// Per element and pass t the leak parameter's gradient takes gv_t * (vp_t * (1 - z_{t-1}) - vo_t) / (1 - lam)  (= gv * dlam below).
+// Its vo half is local.  Its vp half is (gv_t * lam * (1 - z_{t-1})) * vp_t / (lam * (1 - lam)): the first factor is the g_v_prev
+// this cell writes, which the cell of pass t - 1 loads as its carried dL/dv, and vp_t is that cell's v_out.  So the cell of pass
+// t - 1 can pay the vp half of pass t from tensors it streams anyway, and pass t need not read v_prev (128 B per pixel).
+//   FB_LD_SKIP:    this cell leaves its own vp half to the cell of the pass before and does not load v_prev.
+//   FB_LD_COLLECT: the cell of the pass after left its vp half here: add vo * (g_v_in / lam) / (1 - lam)  (g_v_in: the carried dL/dv).
+// Window boundary.  A window's passes run last to first.  Its LAST pass has no carried dL/dv (g_v_out NULL): COLLECT adds nothing,
+// as no later pass of the window exists.  Its FIRST pass has no earlier cell to leave anything to: it runs with COLLECT alone --
+// its own term in the old form (it loads v_prev, the state entering the window; NULL = zero state: the vp half is zero, as before)
+// PLUS the vp half of the second pass.  Every pass in between runs with both bits.  Each pass's vo half is then added once by
+// itself and each pass's vp half once, by the pass before (the first pass's by itself): the same sum as the old form's.  A caller
+// must set COLLECT on pass t - 1 exactly when it set SKIP on pass t, and SKIP only where pass t - 1 runs through these bodies.
+// Small lam.  g_v_in / lam loses the term when lam = sigmoid(leak) underflows.  A thread whose channel quad holds a raw leak
+// parameter below FB_LD_MIN_LEAK (lam < 1.7e-5) honours neither bit for that quad: it keeps loading v_prev and uses the old form on
+// every pass (the parameter, hence the predicate, is the same on all passes of a window).  Decided per thread, from the
+// parameters the kernel loads anyway.
+#define FB_LD_SKIP 16
+#define FB_LD_COLLECT 32
+#define FB_LD_MIN_LEAK (-11.0f)
+
 __device__ __forceinline__ int fb_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 __device__ __forceinline__ float fb_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ uint32_t fb_bf16(float f) {
@@ -688,9 +709,21 @@ __device__ __forceinline__ void fb_body_ws(
   const long slab_off0 = (long)bid * (9 * C32 * C32) + t0 * (C32 * C32) + i, slab_off1 = slab_off0 + C32 * C32;
 
   if (team_e) {
-    float lam[4], th[4], oml[4], inv_oml[4];
+    float lam[4], th[4], oml[4], inv_oml[4], inv_lam[4] = {0, 0, 0, 0};
     float pwa[4] = {0, 0, 0, 0}, pwb[4] = {0, 0, 0, 0};
     float lpt[4] = {0, 0, 0, 0}, apt[4] = {0, 0, 0, 0};  // PLIF: sigma(leak_pt), sigma(add_pt)
+    // the leak gradient's vp half (FB_LD_SKIP / FB_LD_COLLECT above): block-uniform bits, the small-lam predicate per thread --
+    // from the RAW parameters (four loads ahead of the streams; lam itself is computed behind them)
+    // LIF cells only: in the PLIF / XLIF / ALIF kernels the extra state turned 24 spilled registers into 74 (fb_launch masks the bits)
+    constexpr bool LD = !PLIF && !WIN;
+    bool ld_skip = false, ld_collect = false;
+    if (LD && (accumulate & (FB_LD_SKIP | FB_LD_COLLECT))) {
+      bool small = false;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) small |= leak[4 * cg + k] < FB_LD_MIN_LEAK;
+      ld_skip = (accumulate & FB_LD_SKIP) && !small;
+      ld_collect = (accumulate & FB_LD_COLLECT) && !small;
+    }
     // (computed BEHIND the first units' loads: four exp, four divisions and the head's weights are not needed to request them)
     auto constants = [&]() {
 #pragma unroll
@@ -699,6 +732,7 @@ __device__ __forceinline__ void fb_body_ws(
         th[k] = fmaxf(thresh[4 * cg + k], 0.01f);
         oml[k] = 1.0f - lam[k];
         inv_oml[k] = 1.0f / oml[k];
+        if (LD) inv_lam[k] = 1.0f / lam[k];  // (used under ld_collect only: lam >= sigmoid(FB_LD_MIN_LEAK) there)
       }
       if (TOP) {
 #pragma unroll
@@ -774,7 +808,7 @@ __device__ __forceinline__ void fb_body_ws(
         s.gz2 = pgz2[ge];
       }
       s.gv = pgv[ge];
-      s.vp = pvp[ge];
+      if (!LD || !ld_skip) s.vp = pvp[ge];  // (FB_LD_SKIP: not requested -- the cell of the pass before pays this cell's vp half)
       s.zw = pzw[z_prev ? pix0 + pc : 0];
       if (PLIF) {
         sp.gk = pgk[ge];
@@ -822,7 +856,7 @@ __device__ __forceinline__ void fb_body_ws(
       float4 gzb4 = z4;
       if (!TOP && !WIN) gzb4 = has_gz2 ? s.gz2 : z4;
       if (AL && WIN) gzb4 = ks > 0 ? gzxc : z4;
-      const float4 gv4 = WIN ? (ks > 0 ? gvc : z4) : (has_gv ? s.gv : z4), vp4 = (WIN ? w_vp : has_vp) ? s.vp : z4;
+      const float4 gv4 = WIN ? (ks > 0 ? gvc : z4) : (has_gv ? s.gv : z4), vp4 = (WIN ? w_vp : (has_vp && !(LD && ld_skip))) ? s.vp : z4;
       if (TOP && ok) {
         const uint32_t zo = s.zo >> (4 * cg);
 #pragma unroll
@@ -858,9 +892,10 @@ __device__ __forceinline__ void fb_body_ws(
         gc[c] = gv * oml[c];
         gp[c] = gv * lam[c] * (1.0f - z);
         const float cur = (vo[c] - (vp[c] * lam[c]) * (1.0f - z)) * inv_oml[c];
-        const float dlam = vp[c] * (1.0f - z) - cur;
+        const float dlam = vp[c] * (1.0f - z) - cur;  // (FB_LD_SKIP: vp = 0, i.e. the vo half alone, -vo / (1 - lam))
         if (ok) {
           sl[c] += gv * dlam;
+          if (LD && ld_collect) sl[c] += (vo[c] * inv_oml[c]) * (gvo[c] * inv_lam[c]);  // the vp half of the pass after (gvo = 0: none)
           st[c] -= gsp;
         }
       }
@@ -947,6 +982,7 @@ __device__ __forceinline__ void fb_body_ws(
       // consumed the stage -- four half units (two units) of loads in flight, like fb_body's two units
       FbStage s0, s1, s2, s3;
       FbStagePlif pd;  // (LIF only)
+      s0.vp = s1.vp = s2.vp = s3.vp = make_float4(0.f, 0.f, 0.f, 0.f);  // (FB_LD_SKIP: never loaded)
       issue(0, 0, s0, pd);
       issue(0, 1, s1, pd);
       issue(1, 0, s2, pd);
@@ -980,6 +1016,7 @@ __device__ __forceinline__ void fb_body_ws(
       // whole units through three register stages that swap roles (fb_body's pipeline): two units of loads in flight
       FbStage s_cur, s_nxt, s_new;
       FbStagePlif p_cur, p_nxt, p_new;
+      s_cur.vp = s_nxt.vp = s_new.vp = make_float4(0.f, 0.f, 0.f, 0.f);  // (FB_LD_SKIP: never loaded)
       issue(0, 0, s_cur, p_cur);
       issue(1, 0, s_nxt, p_nxt);
       constants();
@@ -1704,6 +1741,37 @@ static int fb_split_blocks(FbJobs& jobs, int n, int nblk, long nunits, bool team
 }
 
 static int fb_diag_select = -1;  // -1 environment / default, 0 k_bwd_diag, 1 k_bwd_diag_ws<4>, 2 k_bwd_diag_ws<8>
+// EVF_BWD_DIAG=fused: every wave through all phases (k_bwd_diag); teams4: 4 + 4 waves; default (teams): 8 + 4 waves
+static int fb_teams_env() {
+  static const int v = []() {
+    const char* e = getenv("EVF_BWD_DIAG");
+    if (e && e[0] == 'f') return 0;
+    return (e && e[0] == 't' && e[5] == '4') ? 1 : 2;
+  }();
+  return v;
+}
+// EVF_BWD_ONE=fused: one cell outside a recording through k_lif_bwd_wgrad (default: the two-team body, a one-entry table)
+static bool fb_one_teams() {
+  static const bool v = []() {
+    const char* e = getenv("EVF_BWD_ONE");
+    return !(e && e[0] == 'f');
+  }();
+  return v;
+}
+// EVF_BWD_LEAK_DEFER=0: the FB_LD_* bits of `accumulate` are ignored -- every cell loads v_prev and forms its whole leak term (A/B)
+static bool fb_leak_defer_env() {
+  static const bool v = []() {
+    const char* e = getenv("EVF_BWD_LEAK_DEFER");
+    return !(e && e[0] == '0');
+  }();
+  return v;
+}
+// 1: the FB_LD_* bits are honoured by every launch a hidden default-neuron cell can take (the two-team bodies); 0: they are ignored.
+// A caller asks once per window and sets the bits on none or all of its passes (SKIP on pass t needs COLLECT on pass t - 1).
+// The evf_plif_* entry points ignore the bits.
+extern "C" int evf_bwd_leak_defer(void) {
+  return (fb_leak_defer_env() && fb_one_teams() && (fb_diag_select < 0 ? fb_teams_env() : fb_diag_select) != 0) ? 1 : 0;
+}
 extern "C" int evf_bwd_diag_select(int which) {
   if (which < -1 || which > 2) return EVF_EINVAL;
   fb_diag_select = which;
@@ -1722,12 +1790,7 @@ static int fb_defer_launch(FbDefer& fb_defer, int d, void* stream) {
     (void)hipFuncSetAttribute((const void*)k_bwd_diag_ws_alif, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
     attr_set = true;
   }
-  // EVF_BWD_DIAG=fused: every wave through all phases (k_bwd_diag); teams4: 4 + 4 waves; default (teams): 8 + 4 waves
-  static const int teams_env = []() {
-    const char* e = getenv("EVF_BWD_DIAG");
-    if (e && e[0] == 'f') return 0;
-    return (e && e[0] == 't' && e[5] == '4') ? 1 : 2;
-  }();
+  const int teams_env = fb_teams_env();
   const bool plif = fb_defer.job[d][0].kind >= 3;  // (a recording holds cells of one neuron model: fb_launch)
   const int teams = plif ? 2 : (fb_diag_select < 0 ? teams_env : fb_diag_select);
   FbJobs jobs;
@@ -1737,6 +1800,9 @@ static int fb_defer_launch(FbDefer& fb_defer, int d, void* stream) {
   static const int cost_env = []() { const char* e = getenv("EVF_BWD_COST"); return e ? atoi(e) : 0; }();  // (A/B measurements)
   const int nblk = fb_blocks_per_cell(nunits, n, cost_env > 0 ? cost_env : (teams == 2 ? 8 : 11));  // (k_bwd_diag_ws<8>: ~4.0 k cycles per unit, phase stamps)
   const int ntot = fb_split_blocks(jobs, n, nblk, nunits, teams == 2);
+  if (teams == 0)  // (k_bwd_diag = fb_body knows no FB_LD_* bits: a cell recorded with them cannot run there)
+    for (int k = 0; k < n; ++k)
+      if (jobs.j[k].accumulate & (FB_LD_SKIP | FB_LD_COLLECT)) return EVF_ENOTSUP;
   evf_prof_mark(1, 0, stream);
   if (plif && jobs.j[0].pl.xl == 2)
     hipLaunchKernelGGL(k_bwd_diag_ws_alif, dim3(ntot), dim3(768), FB_LDS, EVF_STREAM(stream), jobs, fb_defer.B, fb_defer.H,
@@ -1829,7 +1895,8 @@ static int fb_launch(const float* g_z_out, const float* g_z_out2, const FbTop* t
       W <= 0 || ((zT_prev != nullptr) != (slab_rec != nullptr)) || (topp && (g_z_out || zT_prev)) || (topp && g_z_out2))
     return EVF_EINVAL;
   const int row_ld = accumulate >> 8;  // pitch of the per-block parameter-gradient rows (0: dense outputs, atomics)
-  accumulate &= 1;
+  const int ldf = (fb_leak_defer_env() && !plp) ? (accumulate & (FB_LD_SKIP | FB_LD_COLLECT)) : 0;  // (LIF cells: see fb_body_ws)
+  accumulate = (accumulate & 1) | ldf;  // (the bodies test bit 0; the two-team bodies the FB_LD_* bits as well)
   const long nunits = fb_units(B, H, W);
   const int nchunk = (W + FB_CW - 1) / FB_CW;
   const int nrows_all = fb_rows(nunits);
@@ -1862,10 +1929,7 @@ static int fb_launch(const float* g_z_out, const float* g_z_out2, const FbTop* t
   }
   // One cell of the default neuron through the two-team body as well (k_bwd_diag_ws<8> with a one-entry table;
   // EVF_BWD_ONE=fused: k_lif_bwd_wgrad, every wave through all phases)
-  static const bool one_teams = []() {
-    const char* e = getenv("EVF_BWD_ONE");
-    return !(e && e[0] == 'f');
-  }();
+  const bool one_teams = fb_one_teams();
   if (fast && (one_teams || plp) && (g_cur || g_split)) {
     static bool attr_ws = false;
     if (!attr_ws) {
@@ -1889,6 +1953,7 @@ static int fb_launch(const float* g_z_out, const float* g_z_out2, const FbTop* t
       hipLaunchKernelGGL(k_bwd_diag_ws<8>, dim3(nblk), dim3(768), FB_LDS, st, jobs, B, H, W, nchunk, nunits, row_ld, nrows_all);
     return evf_status();
   }
+  if (ldf) return EVF_ENOTSUP;  // (k_lif_bwd_wgrad = fb_body: see evf_bwd_leak_defer)
 #define FB_GO(REC_, TOP_, FAST_, slot)                                                                                    \
   do {                                                                                                                    \
     if (!attr[slot]) {                                                                                                    \

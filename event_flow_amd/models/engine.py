@@ -97,6 +97,7 @@ class _Window:
         self.g_split = None  # [3,B,H,W,32] bf16: exact 3-way split of g_cur (bf16x3 path)
         self.gpt = [None] * n  # PLIF: dL/d(trace) carried to the previous pass
         self.gpt_has = [False] * n
+        self.ld_owed = [None] * n  # leak gradient: the potential half the pass after left to this one (address of its v_prev), see _backward_pass
         self.gP = None  # PLIF: dL/d(pooled pre-synaptic activity) of the layer being processed [B,H,W]
         # small-parameter gradient accumulator: the engine's persistent buffer when FlatAdam owns the gradients (cleared by
         # the kernel that consumes it, _finalize), else fresh zeros
@@ -938,6 +939,17 @@ class FireNetEngine:
                 if use_rec and bool(win.slab_init.get(kr)) != bool(acc_flag):
                     # first recurrent contribution arrives later than the ff one: start its slab at zero
                     _lib.zero_(self._slab(kr, nsl, dev))
+                # leak gradient without the v_prev stream (include/evflow.h, evf_bwd_leak_defer): every pass but the window's first
+                # leaves the half that needs v_prev to the pass before (16), which adds it from its own v_out and carried dL/dv (32)
+                ld_ok = (c.hard_reset and c.activation == "arctanspike" and not trace_fused  # (LIF cells: the evf_plif_* entry points ignore the bits)
+                         and _lib.load().evf_bwd_leak_defer() == 1)
+                if win.ld_owed[i] is not None:
+                    if not ld_ok or g_v is None or v_out.data_ptr() != win.ld_owed[i]:
+                        raise _lib.EvflowError(f"layer {i}: the pass after left its leak-gradient half to a cell that cannot add it")
+                    acc_flag |= 32
+                win.ld_owed[i] = v_prev.data_ptr() if (ld_ok and not is_first and v_prev is not None) else None
+                if win.ld_owed[i] is not None:
+                    acc_flag |= 16
                 if top:
                     _lib.call("evf_plif_bwd_wgrad_top" if trace_fused else "evf_lif_bwd_wgrad_top", _lib.ptr(tape["flow"]), _lib.ptr(g_flow_c), _lib.ptr(self._flat["pred.w"]),
                               _lib.ptr(layers[i][4]), _lib.ptr(self._rowed(win, "pred.w")[0]), _lib.ptr(self._rowed(win, "pred.b")[0]),

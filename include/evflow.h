@@ -362,6 +362,18 @@ int evf_fwd_diag_select(int which);
  * matrix pipes of a SIMD busy at the same time; 512 / 768 threads).  Same state gradients bit for bit; the weight-gradient slabs and per-channel sums agree to
  * fp32 round-off (other partial-sum grouping).  Process-wide. */
 int evf_bwd_diag_select(int which);
+/* The leak gradient of a hidden default-neuron LIF cell without its v_prev stream (evf_lif_bwd_wgrad / 2 / _top; one-pass cells,
+ * recorded or not; the evf_plif_* entry points ignore the bits: their kernels have no registers to spare).  Pass t's term gv * (vp * (1 - z_prev) - v_out) / (1 - lam) has a half that needs vp;
+ * that half equals v_out * (g_v_out / lam) / (1 - lam) at the cell of pass t - 1 (g_v_out there = the g_v_prev pass t wrote).
+ * Two bits of `accumulate`:
+ *   16 (skip):    this cell does not read v_prev; the cell of the pass before adds this cell's vp half.
+ *   32 (collect): add the vp half of the cell of the pass after (nothing when g_v_out is NULL).
+ * Over a window: 16 | 32 on every pass but the first, 32 on the first (it reads the state entering the window and forms its own
+ * term as before).  g_cur, g_split, g_v_prev, g_thresh and the slabs are the same bits; g_leak's terms are grouped by another pass.
+ * Channel quads with a raw leak parameter below -11 (lam < 1.7e-5) ignore both bits (kernel-side, per thread).
+ * evf_bwd_leak_defer(): 1 when the bits are honoured; 0 (environment EVF_BWD_LEAK_DEFER=0, or a kernel choice without the
+ * two-team body: EVF_BWD_DIAG=fused, EVF_BWD_ONE=fused, evf_bwd_diag_select(0)) when they are ignored or refused (EVF_ENOTSUP). */
+int evf_bwd_leak_defer(void);
 /* ... and for a recurrent cell both input gradients in one launch: g_x (+)= conv^T(g_cur, W_ff) as above,
  * g_x2 = conv^T(g_cur, W_rec) (written) -- dL/d(previous output spikes), models/spiking_submodules.py:530. */
 int evf_conv_dgrad_b3_f32_pair(const float* g_cur, const void* wT_b3, float* g_x, int accumulate,
