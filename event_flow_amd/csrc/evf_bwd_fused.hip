@@ -134,6 +134,8 @@ struct FbPlif {
            // 2: an ALIF cell (:230-334, :660-768): the same, with the trace (leak_pt = leak_t) driven by the cell's OWN previous spikes z
            // (un-detached, :311): no pooled activity, and (1 - sigma(leak_t)) * dL/d(t') flows into dL/d(spikes) of the pass BEFORE --
            // a window launch carries it in registers, a one-pass launch writes it to g_zx (the caller hands it back as g_z_out2)
+  int soft;      // XLIF / ALIF cells (xl != 0) with the soft reset, v' = v * lam + (1 - lam) * cur - z * (t0 + t1 * trace before the pass)
+                 // (:430 / :871, :327 / :762): the launchers pick the SOFT instantiations of fb_body_ws (set by fb_launch / fb_window_launch)
   float4* g_zx;  // ALIF, one-pass launches: [B,H,W,32] out (may alias g_z_out2: the same thread reads, then writes)
 };
 
@@ -618,7 +620,9 @@ struct FbWin {
   const uint32_t* z_out[FB_WIN_MAX]; // [B,H,W] the layer's own output spikes
 };
 // AL (PLIF instantiations): ALIF cells, see FbPlif::xl -- a template parameter, so that the PLIF / XLIF kernels keep their registers
-template <bool REC, bool TOP, int EW, bool PLIF = false, bool WIN = false, bool AL = false>
+// SOFT (PLIF instantiations, XLIF / ALIF cells only): the soft reset, FbPlif::soft -- the reset rule is fixed at compile time like the
+// hard one of every other instantiation; its arms are `if constexpr`, so the hard-reset kernels are what they were
+template <bool REC, bool TOP, int EW, bool PLIF = false, bool WIN = false, bool AL = false, bool SOFT = false>
 __device__ __forceinline__ void fb_body_ws(
     const int bid, const int nblk_, const float4* __restrict__ g_z_out, const float4* __restrict__ g_z_out2,
     const float4* __restrict__ g_v_out, const float4* __restrict__ v_out, const float4* __restrict__ v_prev,
@@ -629,6 +633,7 @@ __device__ __forceinline__ void fb_body_ws(
     int row_ld, const FbPlif pl = FbPlif{}, const FbWin* wp = nullptr) {
   static_assert(!PLIF || EW == 8, "PLIF cells: whole-unit stages only");
   static_assert(!AL || PLIF, "ALIF cells run the PLIF body");
+  static_assert(!SOFT || PLIF, "the soft reset: XLIF / ALIF cells of the PLIF body");
   static_assert(!(AL && TOP && !WIN), "ALIF under the prediction head: window launches only (one pass: evf_pred_bwd + the plain cell)");
   static_assert(!WIN || (!REC && EW == 8), "window launches: feed-forward cells");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -875,12 +880,17 @@ __device__ __forceinline__ void fb_body_ws(
       const float gvo[4] = {gv4.x, gv4.y, gv4.z, gv4.w}, vp[4] = {vp4.x, vp4.y, vp4.z, vp4.w};
       const uint32_t zw = ((WIN ? w_zp : has_zw) ? s.zw : 0u) >> (4 * cg);
       float gc[4], gp[4], gsv[4], pov[4] = {0.f, 0.f, 0.f, 0.f};
+      float ppS[SOFT ? 4 : 1], gzs[SOFT ? 4 : 1];  // SOFT: the trace before the pass (in the reset term's threshold), gv * z_prev
       const bool xl = PLIF && pl.xl != 0;  // (cell-uniform)
       if (PLIF) {  // pt' of the forward pass, recomputed (an XLIF cell: it is part of the threshold, t0 + t1 * pt', :419 / :864)
         const float4 pp4 = (WIN ? w_pp : has_pp) ? sp.pp : z4;
         const float pp[4] = {pp4.x, pp4.y, pp4.z, pp4.w};
 #pragma unroll
         for (int c = 0; c < 4; ++c) pov[c] = evf_plif_trace(pp[c], lpt[c], AL ? (float)((zw >> c) & 1u) : sp.P);  // (ALIF: t * leak_t + (1 - leak_t) * z, :311)
+        if constexpr (SOFT) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) ppS[c] = pp[c];
+        }
       }
 #pragma unroll
       for (int c = 0; c < 4; ++c) {  // autograd of spiking_submodules.py:103-126 / :523-551 (hard reset, arctan surrogate)
@@ -890,6 +900,19 @@ __device__ __forceinline__ void fb_body_ws(
         gsv[c] = gsp;
         const float gv = gvo[c] + gsp;
         gc[c] = gv * oml[c];
+        if constexpr (SOFT) {
+          // autograd of v' = v * lam + (1 - lam) * cur - z * (t0 + t1 * pt), z detached, t0 / t1 / pt not (:430 / :871, :327 / :762):
+          // no (1 - z) on dL/dv; t0 takes -gv * z here, t1 and the trace carry their shares in the trace backward below
+          const float thp = th[c] + apt[c] * ppS[c];
+          gp[c] = gv * lam[c];
+          const float cur = (vo[c] - vp[c] * lam[c] + z * thp) * inv_oml[c];
+          const float dlam = vp[c] - cur;
+          gzs[c] = gv * z;
+          if (ok) {
+            sl[c] += gv * dlam;
+            st[c] -= gzs[c] + gsp;
+          }
+        } else {
         gp[c] = gv * lam[c] * (1.0f - z);
         const float cur = (vo[c] - (vp[c] * lam[c]) * (1.0f - z)) * inv_oml[c];
         const float dlam = vp[c] * (1.0f - z) - cur;  // (FB_LD_SKIP: vp = 0, i.e. the vo half alone, -vo / (1 - lam))
@@ -897,6 +920,7 @@ __device__ __forceinline__ void fb_body_ws(
           sl[c] += gv * dlam;
           if (LD && ld_collect) sl[c] += (vo[c] * inv_oml[c]) * (gvo[c] * inv_lam[c]);  // the vp half of the pass after (gvo = 0: none)
           st[c] -= gsp;
+        }
         }
       }
       const long eo = pix0 * 8 + ETHR * h + et;  // = (pix0 + p) * 8 + cg
@@ -922,11 +946,13 @@ __device__ __forceinline__ void fb_body_ws(
           const float gx = xl ? gsv[c] : gc[c];  // what the trace scaled in the forward pass: the threshold's / the current's gradient (negated)
           const float g = gk[c] - apt[c] * gx;
           gq[c] = g * lpt[c];
+          if constexpr (SOFT) gq[c] -= gzs[c] * apt[c];  // the reset term's -z * t1 * pt: straight to the trace before the pass
           gzx[c] = g * (1.0f - lpt[c]);
           gPp += gzx[c];
           if (ok) {
             slp[c] += g * (pp[c] - (AL ? (float)((zw >> c) & 1u) : Pv));
             sap[c] -= gx * po;
+            if constexpr (SOFT) sap[c] -= gzs[c] * pp[c];
           }
         }
         if constexpr (AL) {  // the trace's drive was the cell's own previous spikes: their gradient, to the pass before
@@ -1478,6 +1504,41 @@ __global__ __launch_bounds__(768) void k_bwd_win_alif_top(FbJob J, FbWin Wn, int
                                                nullptr, J.g_v_prev, J.g_leak, J.g_thresh, J.slab_ff, nullptr, J.top, row_ld, J.pl, &Wn);
 }
 
+// XLIF (AL = false) / ALIF cells with the soft reset (FbPlif::soft): the SOFT instantiations of the same bodies, kernels of their
+// own -- the hard-reset kernels above and below keep their code and their registers
+template <bool AL>
+__global__ __launch_bounds__(768) void k_bwd_diag_ws_soft(FbJobs jobs, int B, int H, int W, int nchunk, long nunits, int row_ld,
+                                                          int nrows_total) {
+  const int jb = fb_job_of_block(jobs, (int)blockIdx.x);
+  const FbJob& J = jobs.j[jb];
+  const int bid = (int)blockIdx.x - J.blk0, nblk = J.nblk;
+  if (J.kind == 4) {
+    fb_body_ws<true, false, 8, true, false, AL, true>(bid, nblk, J.g_z, J.g_z2, J.g_v, J.v_out, J.v_prev, J.z_prev, J.xT, J.zT, J.leak,
+                                                      J.thresh, B, H, W, nchunk, nunits, J.width, J.accumulate, nrows_total, J.g_cur, J.g_split,
+                                                      J.g_v_prev, J.g_leak, J.g_thresh, J.slab_ff, J.slab_rec, J.top, row_ld, J.pl);
+    return;
+  }
+  if constexpr (!AL) {  // (an ALIF cell under the prediction head, one pass: not served, fb_launch)
+    if (J.kind == 5) {
+      fb_body_ws<false, true, 8, true, false, false, true>(bid, nblk, J.g_z, J.g_z2, J.g_v, J.v_out, J.v_prev, J.z_prev, J.xT, J.zT, J.leak,
+                                                           J.thresh, B, H, W, nchunk, nunits, J.width, J.accumulate, nrows_total, J.g_cur,
+                                                           J.g_split, J.g_v_prev, J.g_leak, J.g_thresh, J.slab_ff, J.slab_rec, J.top, row_ld,
+                                                           J.pl);
+      return;
+    }
+  }
+  fb_body_ws<false, false, 8, true, false, AL, true>(bid, nblk, J.g_z, J.g_z2, J.g_v, J.v_out, J.v_prev, J.z_prev, J.xT, J.zT, J.leak,
+                                                     J.thresh, B, H, W, nchunk, nunits, J.width, J.accumulate, nrows_total, J.g_cur, J.g_split,
+                                                     J.g_v_prev, J.g_leak, J.g_thresh, J.slab_ff, J.slab_rec, J.top, row_ld, J.pl);
+}
+template <bool TOP, bool AL>
+__global__ __launch_bounds__(768) void k_bwd_win_soft(FbJob J, FbWin Wn, int B, int H, int W, int nchunk, long nunits, int row_ld,
+                                                      int nrows_total) {
+  fb_body_ws<false, TOP, 8, true, true, AL, true>((int)blockIdx.x, (int)gridDim.x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                  nullptr, J.leak, J.thresh, B, H, W, nchunk, nunits, J.width, J.accumulate, nrows_total, nullptr,
+                                                  nullptr, J.g_v_prev, J.g_leak, J.g_thresh, J.slab_ff, nullptr, J.top, row_ld, J.pl, &Wn);
+}
+
 // All passes of a window of ONE feed-forward PLIF cell (fb_body_ws<.., WIN>): a launch of its own
 __global__ __launch_bounds__(768) void k_bwd_win_plif(FbJob J, FbWin Wn, int B, int H, int W, int nchunk, long nunits, int row_ld,
                                                       int nrows_total) {
@@ -1788,6 +1849,8 @@ static int fb_defer_launch(FbDefer& fb_defer, int d, void* stream) {
     (void)hipFuncSetAttribute((const void*)k_bwd_diag_ws<8>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
     (void)hipFuncSetAttribute((const void*)k_bwd_diag_ws_plif, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
     (void)hipFuncSetAttribute((const void*)k_bwd_diag_ws_alif, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
+    (void)hipFuncSetAttribute((const void*)k_bwd_diag_ws_soft<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
+    (void)hipFuncSetAttribute((const void*)k_bwd_diag_ws_soft<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
     attr_set = true;
   }
   const int teams_env = fb_teams_env();
@@ -1804,7 +1867,13 @@ static int fb_defer_launch(FbDefer& fb_defer, int d, void* stream) {
     for (int k = 0; k < n; ++k)
       if (jobs.j[k].accumulate & (FB_LD_SKIP | FB_LD_COLLECT)) return EVF_ENOTSUP;
   evf_prof_mark(1, 0, stream);
-  if (plif && jobs.j[0].pl.xl == 2)
+  if (plif && jobs.j[0].pl.soft && jobs.j[0].pl.xl == 2)
+    hipLaunchKernelGGL(k_bwd_diag_ws_soft<true>, dim3(ntot), dim3(768), FB_LDS, EVF_STREAM(stream), jobs, fb_defer.B, fb_defer.H,
+                       fb_defer.W, nchunk, nunits, fb_defer.row_ld, nrows);
+  else if (plif && jobs.j[0].pl.soft)
+    hipLaunchKernelGGL(k_bwd_diag_ws_soft<false>, dim3(ntot), dim3(768), FB_LDS, EVF_STREAM(stream), jobs, fb_defer.B, fb_defer.H,
+                       fb_defer.W, nchunk, nunits, fb_defer.row_ld, nrows);
+  else if (plif && jobs.j[0].pl.xl == 2)
     hipLaunchKernelGGL(k_bwd_diag_ws_alif, dim3(ntot), dim3(768), FB_LDS, EVF_STREAM(stream), jobs, fb_defer.B, fb_defer.H,
                        fb_defer.W, nchunk, nunits, fb_defer.row_ld, nrows);
   else if (plif)
@@ -1888,8 +1957,12 @@ static int fb_launch(const float* g_z_out, const float* g_z_out2, const FbTop* t
                      const uint32_t* z_prev, const uint32_t* xT, const uint32_t* zT_prev, const float* leak,
                      const float* thresh, int B, int H, int W, int hard_reset, int surrogate, float act_width,
                      float* g_cur, void* g_split, float* g_v_prev, float* g_leak, float* g_thresh, float* slab_ff,
-                     float* slab_rec, int accumulate, void* stream, const FbPlif* plp = nullptr) {
-  if (plp && !(hard_reset != 0 && surrogate == EVF_ARCTAN)) return EVF_ENOTSUP;  // (the trace backward lives in the two-team body)
+                     float* slab_rec, int accumulate, void* stream, const FbPlif* plp_ = nullptr) {
+  // (the trace backward lives in the two-team body: the arctan surrogate with the hard reset, or -- XLIF / ALIF cells -- the soft one)
+  if (plp_ && !((hard_reset != 0 || plp_->xl != 0) && surrogate == EVF_ARCTAN)) return EVF_ENOTSUP;
+  FbPlif pl_arg = plp_ ? *plp_ : FbPlif{};
+  pl_arg.soft = (plp_ && hard_reset == 0) ? 1 : 0;
+  const FbPlif* plp = plp_ ? &pl_arg : nullptr;
   if (plp && plp->xl == 2 && topp) return EVF_ENOTSUP;  // (an ALIF cell under the prediction head, one pass: evf_pred_bwd + evf_plif_bwd_wgrad2)
   if (!v_out || !xT || !leak || !thresh || (!g_cur && !g_split) || !g_v_prev || !g_leak || !g_thresh || !slab_ff || B <= 0 || H <= 0 ||
       W <= 0 || ((zT_prev != nullptr) != (slab_rec != nullptr)) || (topp && (g_z_out || zT_prev)) || (topp && g_z_out2))
@@ -1904,7 +1977,7 @@ static int fb_launch(const float* g_z_out, const float* g_z_out2, const FbTop* t
   hipStream_t st = EVF_STREAM(stream);
   const FbTop top = topp ? *topp : FbTop{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   static bool attr[12] = {false};
-  const bool fast = hard_reset != 0 && surrogate == EVF_ARCTAN;
+  const bool fast = (hard_reset != 0 || plp != nullptr) && surrogate == EVF_ARCTAN;  // (a compile-time neuron; plp: checked above)
   const int bctx = evf_ctx_find(stream);
   const EvfBwdDefer evf_bwd_defer = bctx >= 0 ? evf_bwd_defer_tab[bctx] : EvfBwdDefer{false, 0, false};
   FbDefer& fb_defer = fb_tab[bctx < 0 ? 0 : bctx];
@@ -1914,7 +1987,8 @@ static int fb_launch(const float* g_z_out, const float* g_z_out2, const FbTop* t
     bool same = !any || (fb_defer.B == B && fb_defer.H == H && fb_defer.W == W && fb_defer.row_ld == row_ld);
     for (int d = 0; d < EVF_BWD_DIAGS && same; ++d)
       if (fb_defer.n[d])  // one neuron model per recording
-        same = (fb_defer.job[d][0].kind >= 3) == (plp != nullptr) && (!plp || fb_defer.job[d][0].pl.xl == plp->xl);
+        same = (fb_defer.job[d][0].kind >= 3) == (plp != nullptr) &&
+               (!plp || (fb_defer.job[d][0].pl.xl == plp->xl && fb_defer.job[d][0].pl.soft == plp->soft));
     if (fast && (g_cur || g_split) && same && fb_defer.n[evf_bwd_defer.slot] < FB_MAX_JOBS) {
       fb_defer.B = B, fb_defer.H = H, fb_defer.W = W, fb_defer.row_ld = row_ld;
       FbJob& J = fb_defer.job[evf_bwd_defer.slot][fb_defer.n[evf_bwd_defer.slot]++];
@@ -1936,6 +2010,8 @@ static int fb_launch(const float* g_z_out, const float* g_z_out2, const FbTop* t
       (void)hipFuncSetAttribute((const void*)k_bwd_diag_ws<8>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
       (void)hipFuncSetAttribute((const void*)k_bwd_diag_ws_plif, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
       (void)hipFuncSetAttribute((const void*)k_bwd_diag_ws_alif, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
+      (void)hipFuncSetAttribute((const void*)k_bwd_diag_ws_soft<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
+      (void)hipFuncSetAttribute((const void*)k_bwd_diag_ws_soft<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
       attr_ws = true;
     }
     FbJobs jobs;
@@ -1945,7 +2021,11 @@ static int fb_launch(const float* g_z_out, const float* g_z_out2, const FbTop* t
                   plp ? *plp : FbPlif{}};
     const int nblk = fb_blocks_per_cell(nunits, 1, 8);
     for (int k = 0; k < FB_MAX_JOBS; ++k) jobs.j[k] = J, jobs.j[k].blk0 = k ? 0x7fffffff : 0, jobs.j[k].nblk = nblk;
-    if (plp && plp->xl == 2)
+    if (plp && plp->soft && plp->xl == 2)
+      hipLaunchKernelGGL(k_bwd_diag_ws_soft<true>, dim3(nblk), dim3(768), FB_LDS, st, jobs, B, H, W, nchunk, nunits, row_ld, nrows_all);
+    else if (plp && plp->soft)
+      hipLaunchKernelGGL(k_bwd_diag_ws_soft<false>, dim3(nblk), dim3(768), FB_LDS, st, jobs, B, H, W, nchunk, nunits, row_ld, nrows_all);
+    else if (plp && plp->xl == 2)
       hipLaunchKernelGGL(k_bwd_diag_ws_alif, dim3(nblk), dim3(768), FB_LDS, st, jobs, B, H, W, nchunk, nunits, row_ld, nrows_all);
     else if (plp)
       hipLaunchKernelGGL(k_bwd_diag_ws_plif, dim3(nblk), dim3(768), FB_LDS, st, jobs, B, H, W, nchunk, nunits, row_ld, nrows_all);
@@ -2035,7 +2115,7 @@ extern "C" int evf_plif_bwd_wgrad2(const float* g_z_out, const float* g_z_out2, 
   if (!P || !leak_pt || !add_pt || !g_pt_prev || !g_P_raw || !g_leak_pt || !g_add_pt) return EVF_EINVAL;
   const int xl = (hard_reset >> 1) & 3;  // (bits 1-2 of hard_reset: 1 an XLIF cell, 2 an ALIF cell -- g_P_raw then is g_zx [B,H,W,32])
   const FbPlif pl{(const float4*)g_pt_carry, (const float4*)pt_prev, P, leak_pt, add_pt, (float4*)g_pt_prev, g_P_raw, g_leak_pt, g_add_pt,
-                  xl, xl == 2 ? (float4*)g_P_raw : nullptr};
+                  xl, 0, xl == 2 ? (float4*)g_P_raw : nullptr};
   return fb_launch(g_z_out, g_z_out2, nullptr, g_v_out, v_out, v_prev, z_prev, xT, zT_prev, leak, thresh, B, H, W, hard_reset & 1,
                    surrogate, act_width, g_cur, g_split, g_v_prev, g_leak, g_thresh, slab_ff, slab_rec, accumulate, stream, &pl);
 }
@@ -2051,7 +2131,7 @@ extern "C" int evf_plif_bwd_wgrad_top(const float* flow, const float* g_flow, co
   if (!P || !leak_pt || !add_pt || !g_pt_prev || !g_P_raw || !g_leak_pt || !g_add_pt) return EVF_EINVAL;
   const FbTop top{flow, g_flow, pred_w, z_out, d_pred_w, d_pred_b};
   const FbPlif pl{(const float4*)g_pt_carry, (const float4*)pt_prev, P, leak_pt, add_pt, (float4*)g_pt_prev, g_P_raw, g_leak_pt, g_add_pt,
-                  (hard_reset >> 1) & 3, nullptr};
+                  (hard_reset >> 1) & 3, 0, nullptr};
   return fb_launch(nullptr, nullptr, &top, g_v_out, v_out, v_prev, z_prev, xT, nullptr, leak, thresh, B, H, W, hard_reset & 1, surrogate,
                    act_width, g_cur, g_split, g_v_prev, g_leak, g_thresh, slab_ff, nullptr, accumulate, stream, &pl);
 }
@@ -2070,6 +2150,8 @@ static int fb_window_launch(int np, const void* const* g_z, const void* const* f
                             const float* add_pt, int B, int H, int W, float act_width, float* g_v_prev, float* g_pt_prev, float* g_leak,
                             float* g_thresh, float* g_leak_pt, float* g_add_pt, float* slab_ff, int accumulate, void* stream) {
   const bool top = flow != nullptr, plif = leak_pt != nullptr;
+  const bool soft = (accumulate & 8) != 0;  // (bit 3: the soft reset -- XLIF / ALIF cells only, like evf_plif_bwd_wgrad2)
+  if (soft && !(plif && ((accumulate >> 1) & 3) != 0)) return EVF_ENOTSUP;
   if (np < 1 || np > FB_WIN_MAX || (!top && !g_z) || !v_out || !v_prev || !z_prev || !xT || (!g_cur && !g_split) || !leak || !thresh ||
       !g_leak || !g_thresh || !slab_ff || B <= 0 || H <= 0 || W <= 0 || (top && (!g_flow || !z_out || !pred_w || !d_pred_w || !d_pred_b)) ||
       (plif && (!pt_prev || !P || !g_P_raw || !add_pt || !g_leak_pt || !g_add_pt)))
@@ -2098,7 +2180,7 @@ static int fb_window_launch(int np, const void* const* g_z, const void* const* f
   J.width = act_width, J.accumulate = accumulate & 1, J.kind = (top ? 2 : 0) + (plif ? 3 : 0);
   J.top = FbTop{nullptr, nullptr, pred_w, nullptr, d_pred_w, d_pred_b};
   J.pl = FbPlif{nullptr, nullptr, nullptr, leak_pt, add_pt, (float4*)g_pt_prev, nullptr, g_leak_pt, g_add_pt,
-                (accumulate >> 1) & 3, nullptr};  // (bits 1-2 of accumulate: 1 an XLIF cell, 2 an ALIF cell)
+                (accumulate >> 1) & 3, soft ? 1 : 0, nullptr};  // (bits 1-2 of accumulate: 1 an XLIF cell, 2 an ALIF cell)
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)k_bwd_win_plif, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
@@ -2107,13 +2189,21 @@ static int fb_window_launch(int np, const void* const* g_z, const void* const* f
     (void)hipFuncSetAttribute((const void*)k_bwd_win_alif_top, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
     (void)hipFuncSetAttribute((const void*)k_bwd_win_lif, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
     (void)hipFuncSetAttribute((const void*)k_bwd_win_lif_top, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
+    (void)hipFuncSetAttribute((const void*)k_bwd_win_soft<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
+    (void)hipFuncSetAttribute((const void*)k_bwd_win_soft<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
+    (void)hipFuncSetAttribute((const void*)k_bwd_win_soft<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
+    (void)hipFuncSetAttribute((const void*)k_bwd_win_soft<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
     attr = true;
   }
   // blocks: as a one-cell launch whose units cost np times as much (whole rounds of one block per CU)
   const int nblk = fb_blocks_per_cell(nunits, 1, 8 * np);
   evf_prof_mark(8, 0, stream);
 #define FB_WIN_GO(K_) hipLaunchKernelGGL(K_, dim3(nblk), dim3(768), FB_LDS, EVF_STREAM(stream), J, Wn, B, H, W, nchunk, nunits, row_ld, fb_rows(nunits))
-  if (plif && J.pl.xl == 2) {
+  if (soft && J.pl.xl == 2) {
+    if (top) FB_WIN_GO((k_bwd_win_soft<true, true>)); else FB_WIN_GO((k_bwd_win_soft<false, true>));
+  } else if (soft) {
+    if (top) FB_WIN_GO((k_bwd_win_soft<true, false>)); else FB_WIN_GO((k_bwd_win_soft<false, false>));
+  } else if (plif && J.pl.xl == 2) {
     if (top) FB_WIN_GO(k_bwd_win_alif_top); else FB_WIN_GO(k_bwd_win_alif);
   } else if (plif) {
     if (top) FB_WIN_GO(k_bwd_win_plif_top); else FB_WIN_GO(k_bwd_win_plif);

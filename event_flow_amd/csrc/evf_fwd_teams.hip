@@ -85,9 +85,11 @@ extern "C" int evf_debug_ft_stamps(void* dst) { return evf_hip(hipMemcpyFromSymb
 // writes the tape only: per pixel and pass 128 (+128 + 4 PLIF) bytes written and the 4-byte input words read, instead of the
 // potential (+ trace) read back as well.  Team M is the diagonal form's with the halo source and the pass advancing per round.
 // Same expressions in the same order: bit-identical to the cells launched one by one.
-// XL (PLIF instantiations with the hard reset): XLIF cells -- a compile-time switch; as a run-time (cell-uniform) branch it cost the
+// XL (PLIF instantiations): XLIF cells -- a compile-time switch; as a run-time (cell-uniform) branch it cost the
 // PLIF chain kernel 3 % (the round holds both formulas' values live: 168 registers, spills).
 // XL = 2: ALIF cells (FwJob::xl): the XLIF arithmetic with the trace driven by the lane's own previous spike bits instead of the pooled activity.
+// XL != 0 with HARD = false: the soft reset of these cells, - z * (t0 + t1 * trace BEFORE the pass) (:430 / :871, :327 / :762), in the
+// general element loop (WIN: the trace before the pass is the register set's, like the potential).
 template <bool HARD, bool FULL, bool PLIF, bool WIN, class JOBS, class WT, int XL = 0>
 __device__ __forceinline__ void ft_body(const JOBS& jobs, const FtPlan& plan, const int B, const int H, const int W, const WT& wt) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -845,6 +847,10 @@ int evf_fwd_diag_t_launch(const FwJobs& jobs, int n, int B, int H, int W, void* 
     (void)hipFuncSetAttribute((const void*)k_fwd_diag_t<true, false, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
     (void)hipFuncSetAttribute((const void*)k_fwd_diag_t<true, true, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
     (void)hipFuncSetAttribute((const void*)k_fwd_diag_t<true, false, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
+    (void)hipFuncSetAttribute((const void*)k_fwd_diag_t<false, true, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
+    (void)hipFuncSetAttribute((const void*)k_fwd_diag_t<false, false, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
+    (void)hipFuncSetAttribute((const void*)k_fwd_diag_t<false, true, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
+    (void)hipFuncSetAttribute((const void*)k_fwd_diag_t<false, false, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
     attr_set = true;
   }
   // relative cost of a round: feed-forward / recurrent cell / feed-forward cell with the prediction head in team E's epilogue (its
@@ -860,8 +866,8 @@ int evf_fwd_diag_t_launch(const FwJobs& jobs, int n, int B, int H, int W, void* 
   int nhard = 0, nplif = 0;
   for (int k = 0; k < n; ++k) nhard += jobs.j[k].hard_reset ? 1 : 0, nplif += jobs.j[k].leak_pt ? 1 : 0;
   if ((nhard != 0 && nhard != n) || (nplif != 0 && nplif != n)) return EVF_EINVAL;
-  for (int k = 0; k < n; ++k)  // XLIF cells: one kind per launch, hard reset (the caller then runs the cells one by one: evf_fwd_b3.hip)
-    if (jobs.j[k].xl != jobs.j[0].xl || (jobs.j[k].xl && !jobs.j[k].hard_reset)) return EVF_EINVAL;
+  for (int k = 0; k < n; ++k)  // XLIF / ALIF cells: one kind per launch (the caller then runs the cells one by one: evf_fwd_b3.hip)
+    if (jobs.j[k].xl != jobs.j[0].xl) return EVF_EINVAL;
   FtPlan plan;
   plan.njobs = n, plan.ntx = evf_cdiv(W, TW), plan.nyy = evf_cdiv(H, 2);
   const long nstrips = (long)plan.ntx * plan.nyy * B;
@@ -887,9 +893,9 @@ int evf_fwd_diag_t_launch(const FwJobs& jobs, int n, int B, int H, int W, void* 
 #define FT_GO(HARD_, FULL_)                                                                                                  \
   do {                                                                                                                       \
     if (nplif && jobs.j[0].xl == 2)                                                                                          \
-      hipLaunchKernelGGL((k_fwd_diag_t<true, FULL_, true, 2>), dim3(nblk), dim3(FT_THREADS), FT_LDS, st, jobs, plan, B, H, W); \
+      hipLaunchKernelGGL((k_fwd_diag_t<HARD_, FULL_, true, 2>), dim3(nblk), dim3(FT_THREADS), FT_LDS, st, jobs, plan, B, H, W); \
     else if (nplif && jobs.j[0].xl)                                                                                          \
-      hipLaunchKernelGGL((k_fwd_diag_t<true, FULL_, true, 1>), dim3(nblk), dim3(FT_THREADS), FT_LDS, st, jobs, plan, B, H, W); \
+      hipLaunchKernelGGL((k_fwd_diag_t<HARD_, FULL_, true, 1>), dim3(nblk), dim3(FT_THREADS), FT_LDS, st, jobs, plan, B, H, W); \
     else if (nplif)                                                                                                          \
       hipLaunchKernelGGL((k_fwd_diag_t<HARD_, FULL_, true>), dim3(nblk), dim3(FT_THREADS), FT_LDS, st, jobs, plan, B, H, W);  \
     else                                                                                                                     \
@@ -907,7 +913,6 @@ int evf_fwd_diag_t_launch(const FwJobs& jobs, int n, int B, int H, int W, void* 
 int evf_fwd_win_is_chain(const FwJob* c, int n) {
   if (n < 2 || n > FW_WIN_MAX) return 0;
   if (c[0].wrec) return 0;
-  if (c[0].xl && !c[0].hard_reset) return 0;  // (XLIF / ALIF cells with the soft reset: the one-cell kernel)
   for (int k = 1; k < n; ++k) {
     const FwJob &a = c[k - 1], &b = c[k];
     if (b.wrec || b.wff != a.wff || b.leak != a.leak || b.thresh != a.thresh || b.hard_reset != a.hard_reset ||
@@ -940,6 +945,10 @@ int evf_fwd_win_t_launch(const FwJob* cells, int n, int B, int H, int W, void* s
     (void)hipFuncSetAttribute((const void*)k_fwd_win_t<true, false, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
     (void)hipFuncSetAttribute((const void*)k_fwd_win_t<true, true, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
     (void)hipFuncSetAttribute((const void*)k_fwd_win_t<true, false, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
+    (void)hipFuncSetAttribute((const void*)k_fwd_win_t<false, true, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
+    (void)hipFuncSetAttribute((const void*)k_fwd_win_t<false, false, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
+    (void)hipFuncSetAttribute((const void*)k_fwd_win_t<false, true, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
+    (void)hipFuncSetAttribute((const void*)k_fwd_win_t<false, false, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
     attr_set = true;
   }
   FwJob1 job;
@@ -971,9 +980,9 @@ int evf_fwd_win_t_launch(const FwJob* cells, int n, int B, int H, int W, void* s
 #define FT_GO(HARD_, FULL_)                                                                                                     \
   do {                                                                                                                          \
     if (plif && cells[0].xl == 2)                                                                                               \
-      hipLaunchKernelGGL((k_fwd_win_t<true, FULL_, true, 2>), dim3(nblk), dim3(FT_THREADS), FT_LDS, st, job, wt, plan, B, H, W); \
+      hipLaunchKernelGGL((k_fwd_win_t<HARD_, FULL_, true, 2>), dim3(nblk), dim3(FT_THREADS), FT_LDS, st, job, wt, plan, B, H, W); \
     else if (plif && cells[0].xl)                                                                                               \
-      hipLaunchKernelGGL((k_fwd_win_t<true, FULL_, true, 1>), dim3(nblk), dim3(FT_THREADS), FT_LDS, st, job, wt, plan, B, H, W); \
+      hipLaunchKernelGGL((k_fwd_win_t<HARD_, FULL_, true, 1>), dim3(nblk), dim3(FT_THREADS), FT_LDS, st, job, wt, plan, B, H, W); \
     else if (plif)                                                                                                              \
       hipLaunchKernelGGL((k_fwd_win_t<HARD_, FULL_, true>), dim3(nblk), dim3(FT_THREADS), FT_LDS, st, job, wt, plan, B, H, W);   \
     else                                                                                                                        \

@@ -177,11 +177,15 @@ __device__ __forceinline__ void lif_load_prev(int b, int row, int x0, int H, int
   }
 }
 
-// thx: NULL, or the 16 per-element increments of the threshold (XLIF head: t1 * pt', spiking_submodules.py:419; hard reset only)
+// thx: NULL, or the 16 per-element increments of the threshold (XLIF head: t1 * pt', spiking_submodules.py:419)
+// THP (a compile-time switch: the other callers' code does not depend on what the inliner folds): thp = those of the pass before
+// (t1 * pt), the threshold in the soft reset of an XLIF / ALIF head (:430, :327)
+template <bool THP = false>
 __device__ __forceinline__ void lif_update(const f32x16& acc, const float (&vpv)[16], const uint32_t (&zw)[16], int b,
                                            int row, int x0, int H, int W, int lane, float lam, float th, int hard_reset,
                                            float* __restrict__ v_out, uint32_t* __restrict__ z_out,
-                                           uint32_t* __restrict__ zT_out, const float* thx = nullptr) {
+                                           uint32_t* __restrict__ zT_out, const float* thx = nullptr,
+                                           const float* thp = nullptr) {
   const int j = lane & 31;
   const bool row_ok = row < H;
   uint32_t plane = 0u;  // this channel's spikes over the tile's 32 pixels (bit = column)
@@ -196,7 +200,8 @@ __device__ __forceinline__ void lif_update(const f32x16& acc, const float (&vpv)
       const float z = (float)((zw[r] >> j) & 1u);
       const float cur = acc[r];
       const float vo_hard = (v * lam) * (1.0f - z) + (1.0f - lam) * cur;
-      const float vo_soft = v * lam + (1.0f - lam) * cur - z * th;
+      float vo_soft = v * lam + (1.0f - lam) * cur - z * th;
+      if constexpr (THP) vo_soft = v * lam + (1.0f - lam) * cur - z * (th + thp[r]);
       const float vo = hard_reset ? vo_hard : vo_soft;  // (a select, not a branch, inside the unrolled pixel loop)
       v_out[pix * C32 + j] = vo;
       spike = (vo - (thx ? th + thx[r] : th)) > 0.f;
@@ -316,7 +321,9 @@ extern "C" int evf_conv_lif_fwd(const uint32_t* x, const float* w_ff, const floa
 // Head: real-valued NCHW input with few channels (event counts / voxels).
 // K = 9 taps x Cin; one MFMA k-step covers channels (2s, 2s+1).
 #define HEAD_MAX_CIN 8
-template <int S2>  // S2 = ceil(Cin / 2): compile-time trip counts, so that every staging load of a thread is in flight at once
+// XLS: an XLIF / ALIF head with the soft reset (evf_head_plif_fwd, bit 0 of the flag clear with mode 1 or 2) -- the trace before the
+// pass, already loaded for the trace update, stays as the reset term's threshold increments; an instantiation of its own
+template <int S2, bool XLS = false>  // S2 = ceil(Cin / 2): compile-time trip counts, so that every staging load of a thread is in flight at once
 __global__ __launch_bounds__(256) void k_head_lif_fwd(const float* __restrict__ x, const float* __restrict__ w,
                                                       const float* __restrict__ leak, const float* __restrict__ thresh,
                                                       const float* __restrict__ v_prev,
@@ -389,6 +396,7 @@ __global__ __launch_bounds__(256) void k_head_lif_fwd(const float* __restrict__ 
   const bool al = pt_out && ((hard_reset >> 1) & 3) == 2;  // ALIF: the trace is driven by the cell's own previous spikes (:311)
   hard_reset &= 1;
   float thx0[16], thx1[16];  // (XLIF: t1 * pt' per element of the wave's two rows)
+  float thp0[XLS ? 16 : 1], thp1[XLS ? 16 : 1];  // (soft reset: t1 * pt, the increments of the pass before)
   if (pt_out) {  // PLIF head (spiking_submodules.py:191-227): cur = ff - sigma(add_pt) * pt'
     const int py = tid >> 5, px = tid & 31;
     float sum9 = 0.f;
@@ -421,12 +429,16 @@ __global__ __launch_bounds__(256) void k_head_lif_fwd(const float* __restrict__ 
         const float zprev = (float)((((m ? zw1 : zw0)[r]) >> j) & 1u);
         const float pto = evf_plif_trace(pt_prev ? ptv[r] : 0.f, lpt, al ? zprev : s_P[(r0 + m) * TW + cl]);
         thx[r] = apt * pto;
+        if constexpr (XLS) (m ? thp1 : thp0)[r] = apt * (pt_prev ? ptv[r] : 0.f);
         if (!xl) acc[r] = acc[r] - thx[r];  // (XLIF: the current stays ff, the threshold becomes t0 + t1 * pt', :419)
         if (row < H && col < W) pt_out[(((long)b * H + row) * W + col) * C32 + j] = pto;
       }
     }
   }
-  if (xl) {  // (block-uniform)
+  if constexpr (XLS) {
+    lif_update<true>(acc0, vp0, zw0, b, y0 + r0, x0, H, W, lane, lam, th, 0, v_out, z_out, zT_out, thx0, thp0);
+    lif_update<true>(acc1, vp1, zw1, b, y0 + r0 + 1, x0, H, W, lane, lam, th, 0, v_out, z_out, zT_out, thx1, thp1);
+  } else if (xl) {  // (block-uniform)
     lif_update(acc0, vp0, zw0, b, y0 + r0, x0, H, W, lane, lam, th, hard_reset, v_out, z_out, zT_out, thx0);
     lif_update(acc1, vp1, zw1, b, y0 + r0 + 1, x0, H, W, lane, lam, th, hard_reset, v_out, z_out, zT_out, thx1);
   } else {
@@ -439,9 +451,11 @@ static void launch_head_fwd(dim3 grid, dim3 block, hipStream_t st, const float* 
                             const float* thresh, const float* v_prev, const uint32_t* z_prev, int B, int Cin, int H, int W,
                             int hard_reset, float* v_out, uint32_t* z_out, uint32_t* zT_out, const float* leak_pt,
                             const float* add_pt, const float* pt_prev, float* pt_out, float* P_out) {
-#define HEAD_FWD(S2)                                                                                                       \
-  hipLaunchKernelGGL(k_head_lif_fwd<S2>, grid, block, 0, st, x, w, leak, thresh, v_prev, z_prev, B, Cin, H, W, hard_reset, \
-                     v_out, z_out, zT_out, leak_pt, add_pt, pt_prev, pt_out, P_out)
+#define HEAD_FWD_(S2, XLS_)                                                                                                 \
+  hipLaunchKernelGGL((k_head_lif_fwd<S2, XLS_>), grid, block, 0, st, x, w, leak, thresh, v_prev, z_prev, B, Cin, H, W,       \
+                     hard_reset, v_out, z_out, zT_out, leak_pt, add_pt, pt_prev, pt_out, P_out)
+#define HEAD_FWD(S2) do { if (xls) HEAD_FWD_(S2, true); else HEAD_FWD_(S2, false); } while (0)
+  const bool xls = pt_out && (hard_reset & 6) && !(hard_reset & 1);  // (an XLIF / ALIF head with the soft reset)
   switch ((Cin + 1) / 2) {
     case 1: HEAD_FWD(1); break;
     case 2: HEAD_FWD(2); break;
@@ -449,6 +463,7 @@ static void launch_head_fwd(dim3 grid, dim3 block, hipStream_t st, const float* 
     default: HEAD_FWD(4); break;
   }
 #undef HEAD_FWD
+#undef HEAD_FWD_
 }
 
 // ---- the head layer of a whole WINDOW in one launch -----------------------------------------------------------------
@@ -483,11 +498,14 @@ struct HeadWin {
 // holds potential (+ trace) and accumulators of 32 pixels per lane: 212 registers (LIF) / 288 wanted (PLIF, i.e. one wave per
 // SIMD or spills) -- the block then runs at the latency of its own store -> barrier -> matrix chain.  One row per wave halves the
 // per-lane state; twice the waves per CU hide each other's chains.  Same MFMA order per row: the same bits.
-template <int S2, bool PLIF = false, int NWV = 4>
+// XLS: an XLIF / ALIF head with the soft reset (k_head_lif_fwd<.., XLS>): the reset term's threshold t0 + t1 * pt of the pass before, from
+// the trace the registers hold when the pass begins
+template <int S2, bool PLIF = false, int NWV = 4, bool XLS = false>
 // (second launch bound = waves per SIMD: LIF x 8 waves 130 -> 128 registers = two blocks per CU; PLIF x 4 waves: two blocks, spills)
 __global__ __launch_bounds__(64 * NWV, (NWV == 8 && !PLIF) ? 4 : ((NWV == 4 && PLIF) ? 2 : 1)) void k_head_lif_fwd_win(HeadWin a) {
   constexpr int NTHR = 64 * NWV, RPW = TH / NWV;  // threads, rows per wave
   static_assert(TH == 8 && TW == 32 && (NWV == 4 || NWV == 8), "8 x 32 tile");
+  static_assert(!XLS || PLIF, "the soft reset of an XLIF / ALIF head: the PLIF form");
   __shared__ float s_x[2][2 * S2][HALO_H * HALO_W];
   __shared__ float s_w[9 * S2 * 64];
   __shared__ float s_P[PLIF ? TH * TW : 1];
@@ -580,8 +598,9 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 && !PLIF) ? 4 : ((NWV == 4 && P
   // inside the image (block-uniform) -- no per-pixel branch.  The 16 spike words of the row go out in ONE store (lane r of
   // each half wave keeps word r) instead of 16 stores by lanes 0 and 32.
   // ptr: the row's new traces (PLIF / XLIF; XLIF: threshold t0 + t1 * pt' per element, spiking_submodules.py:419, hard reset only)
+  // tpr (XLS): t1 * pt of the pass before per element (the soft reset's threshold increments)
   auto update = [&](const f32x16& acc, float (&vpv)[16], uint32_t& zbr, int row, const HeadWinPass& o, const bool FULL,
-                    const float (&ptr)[16]) {
+                    const float (&ptr)[16], const float (&tpr)[XLS ? 16 : 1]) {
     const bool row_ok = FULL || row < H;
     uint32_t plane = 0u, znew = 0u, zsel = 0u;
     // one base address per row; pixel r of the lane is a compile-time offset from it ((r & 3) + 8 (r >> 2) pixels)
@@ -596,7 +615,8 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 && !PLIF) ? 4 : ((NWV == 4 && P
         const float z = (float)((zbr >> r) & 1u);
         const float cur = acc[r];
         const float vo_hard = (v * lam) * (1.0f - z) + (1.0f - lam) * cur;
-        const float vo_soft = v * lam + (1.0f - lam) * cur - z * th;
+        float vo_soft = v * lam + (1.0f - lam) * cur - z * th;
+        if constexpr (XLS) vo_soft = v * lam + (1.0f - lam) * cur - z * (th + tpr[XLS ? r : 0]);
         const float vo = hard_reset ? vo_hard : vo_soft;
         vrow[((r & 3) + 8 * (r >> 2)) * C32] = vo;
         spike = (vo - ((PLIF && xl) ? th + apt * ptr[r] : th)) > 0.f;
@@ -641,6 +661,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 && !PLIF) ? 4 : ((NWV == 4 && P
     // order: it also covers the stores of pass t - 1, which have had a whole matrix phase to drain) then leaves pass t's stores
     // in flight across the barrier and the next matrix phase.  (s_x[buf ^ 1] was last read in pass t - 1, before this pass's barrier.)
     if (t + 1 < a.np) put_x(buf ^ 1);
+    float tp[XLS ? RPW : 1][XLS ? 16 : 1];
     if (PLIF) {  // cur = ff - sigma(add_pt) * pt' (k_head_lif_fwd, spiking_submodules.py:191-227)
       if (tid < TH * TW) {
         const int py = tid >> 5, px = tid & 31;
@@ -665,6 +686,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 && !PLIF) ? 4 : ((NWV == 4 && P
           const int cl = mfma_row(r, lane), col = x0 + cl;
           const float pto = evf_plif_trace(pt[PLIF ? m : 0][r], lpt, al ? (float)((zb[m] >> r) & 1u) : s_P[(r0 + m) * TW + cl]);
           if (!xl) acc[m][r] = acc[m][r] - apt * pto;  // (XLIF / ALIF: the current stays ff)
+          if constexpr (XLS) tp[m][r] = apt * pt[m][r];
           pt[PLIF ? m : 0][r] = pto;
           if (row < H && col < W) prow[cl * C32] = pto;
         }
@@ -672,8 +694,8 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 && !PLIF) ? 4 : ((NWV == 4 && P
     }
 #pragma unroll
     for (int m = 0; m < RPW; ++m) {
-      if (full) update(acc[m], vp[m], zb[m], y0 + r0 + m, a.p[t], true, pt[PLIF ? m : 0]);
-      else update(acc[m], vp[m], zb[m], y0 + r0 + m, a.p[t], false, pt[PLIF ? m : 0]);
+      if (full) update(acc[m], vp[m], zb[m], y0 + r0 + m, a.p[t], true, pt[PLIF ? m : 0], tp[XLS ? m : 0]);
+      else update(acc[m], vp[m], zb[m], y0 + r0 + m, a.p[t], false, pt[PLIF ? m : 0], tp[XLS ? m : 0]);
     }
   }
 }
@@ -745,7 +767,20 @@ int evf_hf_defer_launch(int ctx, void* stream) {
     if (waves == 8) hipLaunchKernelGGL((k_head_lif_fwd_win<S2_, PLIF_, 8>), grid, block, 0, st, a);        \
     else hipLaunchKernelGGL((k_head_lif_fwd_win<S2_, PLIF_, 4>), grid, block, 0, st, a);                   \
   } while (0)
-      if (f.pt_out) {
+      if (f.pt_out && (f.hard_reset & 6) && !(f.hard_reset & 1)) {  // (an XLIF / ALIF head with the soft reset)
+#define HEAD_FWD_WIN_S(S2_)                                                                               \
+  do {                                                                                                    \
+    if (waves == 8) hipLaunchKernelGGL((k_head_lif_fwd_win<S2_, true, 8, true>), grid, block, 0, st, a);   \
+    else hipLaunchKernelGGL((k_head_lif_fwd_win<S2_, true, 4, true>), grid, block, 0, st, a);              \
+  } while (0)
+        switch ((f.Cin + 1) / 2) {
+          case 1: HEAD_FWD_WIN_S(1); break;
+          case 2: HEAD_FWD_WIN_S(2); break;
+          case 3: HEAD_FWD_WIN_S(3); break;
+          default: HEAD_FWD_WIN_S(4); break;
+        }
+#undef HEAD_FWD_WIN_S
+      } else if (f.pt_out) {
         switch ((f.Cin + 1) / 2) {
           case 1: HEAD_FWD_WIN(1, true); break;
           case 2: HEAD_FWD_WIN(2, true); break;
@@ -804,7 +839,6 @@ extern "C" int evf_head_plif_fwd(const float* x, const float* w, const float* le
   if (!x || !w || !leak_v || !leak_pt || !add_pt || !thresh || !v_out || !z_out || !pt_out || !P_out || B <= 0 ||
       Cin <= 0 || Cin > HEAD_MAX_CIN || H <= 0 || W <= 0)
     return EVF_EINVAL;
-  if ((hard_reset & 6) && !(hard_reset & 1)) return EVF_ENOTSUP;  // (an XLIF / ALIF head with the soft reset: its threshold of the pass before is not kept here)
   const int fctx = evf_ctx_find(stream);
   if (fctx >= 0 && evf_fwd_defer_active(fctx)) {  // recorded like evf_head_lif_fwd: the window's passes in one launch at the flush
     HfDefer& hf = hf_tab[fctx];
@@ -1159,7 +1193,9 @@ struct HeadBwdKeepPlif {
 // a run-time flag the PLIF window kernel kept eight more values live across the element loop and spilled (401 -> 628 us per window)
 // XL = 2: an ALIF head (spiking_submodules.py:230-334) -- the XLIF arithmetic with the trace driven by the cell's OWN previous spikes
 // (un-detached, :311): their gradient (1 - sigma(leak_t)) * dL/d(t') goes to the pass before through the buffer HeadPlifPass::P.
-template <bool FAST, int NT = 0, bool FIRST = true, bool PLIF = false, int XL = 0>
+// SOFT (XL != 0 only): the soft reset fixed at compile time, - z * (t0 + t1 * trace before the pass) (:430, :327) -- FAST's sibling for
+// the reference's default XLIF / ALIF cells; its arms are `if constexpr`, the other instantiations are what they were
+template <bool FAST, int NT = 0, bool FIRST = true, bool PLIF = false, int XL = 0, bool SOFT = false>
 __device__ __forceinline__ void head_bwd_pass(
     const float4* g_z_out, const float4* g_v_out, const float4* v_out, const float4* v_prev, const uint32_t* z_prev,
     const float* __restrict__ leak, const float* __restrict__ thresh, long npix, int hard_reset_rt, int surrogate_rt, float width,
@@ -1167,7 +1203,8 @@ __device__ __forceinline__ void head_bwd_pass(
     float* slab, int slab_acc, int row_ld, float4 (&gvc)[NT ? NT : 1], float4 (&voc)[NT ? NT : 1], int (&xo)[NT ? NT : 1][4],
     HeadBwdKeep& K, bool store_gv,  // store_gv: the launch's last pass (NT = 0: every pass is first and last)
     const HeadPlifPass pq = HeadPlifPass{}, const HeadPlifPrm pm = HeadPlifPrm{}, float4* gpc_ = nullptr, HeadBwdKeepPlif* KP_ = nullptr) {
-  const int hard_reset = FAST ? 1 : (hard_reset_rt & 1), surrogate = FAST ? EVF_ARCTAN : surrogate_rt;
+  static_assert(!SOFT || (FAST && PLIF && XL != 0), "the compile-time soft reset: XLIF / ALIF heads, arctan surrogate");
+  const int hard_reset = SOFT ? 0 : (FAST ? 1 : (hard_reset_rt & 1)), surrogate = FAST ? EVF_ARCTAN : surrogate_rt;
   constexpr bool xl = PLIF && XL != 0, al = PLIF && XL == 2;
   float4* const gzxb = al ? (float4*)pq.P : nullptr;
   const bool has_gx = al && (FIRST ? pq.g_pt_out != nullptr : true);  // (a pass after this one exists: its g_zx is in the buffer)
@@ -1304,11 +1341,16 @@ __device__ __forceinline__ void head_bwd_pass(
     const float vo[4] = {vo4.x, vo4.y, vo4.z, vo4.w}, gz[4] = {gz4.x, gz4.y, gz4.z, gz4.w};
     const float gvo[4] = {gv4.x, gv4.y, gv4.z, gv4.w}, vp[4] = {vp4.x, vp4.y, vp4.z, vp4.w};
     float gc[4], gp[4], gsv[xl ? 4 : 1], pov[xl ? 4 : 1];
+    float ppS[SOFT ? 4 : 1], gzs[SOFT ? 4 : 1];  // SOFT: the trace before the pass (in the reset term's threshold), gv * z_prev
     if constexpr (xl) {  // pt' of the forward pass, recomputed: it is part of the threshold
       const float4 pp4 = pq.pt_prev ? in.ppl : zero4;
       const float pp[4] = {pp4.x, pp4.y, pp4.z, pp4.w};
 #pragma unroll
       for (int k = 0; k < 4; ++k) pov[k] = evf_plif_trace(pp[k], KP.lpt[k], al ? (float)((zw >> k) & 1u) : in.Pl);
+      if constexpr (SOFT) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ppS[k] = pp[k];
+      }
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -1321,7 +1363,13 @@ __device__ __forceinline__ void head_bwd_pass(
       const float gv = gvo[k] + gsp;
       gc[k] = gv * oml[k];
       float cur, dlam, dth = 0.f;
-      if (hard_reset) {
+      if constexpr (SOFT) {  // z detached, t0 / t1 / the trace not: t1 and the trace take their shares in the trace backward below
+        gp[k] = gv * lam[k];
+        cur = (vo[k] - vp[k] * lam[k] + z * (th[k] + KP.apt[k] * ppS[k])) * inv_oml[k];
+        dlam = vp[k] - cur;
+        dth = gv * z;
+        gzs[k] = dth;
+      } else if (hard_reset) {
         gp[k] = gv * lam[k] * (1.0f - z);
         cur = (vo[k] - (vp[k] * lam[k]) * (1.0f - z)) * inv_oml[k];
         dlam = vp[k] * (1.0f - z) - cur;
@@ -1353,10 +1401,12 @@ __device__ __forceinline__ void head_bwd_pass(
         else po = evf_plif_trace(pp[k], KP.lpt[k], Pv), gx = gc[k];
         const float g = gk[k] - KP.apt[k] * gx;
         gq[k] = g * KP.lpt[k];
+        if constexpr (SOFT) gq[k] -= gzs[k] * KP.apt[k];  // the reset term's -z * t1 * pt: straight to the trace before the pass
         if constexpr (al) gzx[k] = g * (1.0f - KP.lpt[k]);
         if (ok) {
           KP.slp[k] += g * (pp[k] - (al ? (float)((zw >> k) & 1u) : Pv));
           KP.sap[k] -= gx * po;
+          if constexpr (SOFT) KP.sap[k] -= gzs[k] * pp[k];
         }
       }
       if constexpr (al) {
@@ -1488,7 +1538,7 @@ __global__ __launch_bounds__(256) void k_head_bwd_mfma(
 }
 
 // PLIF head, one pass: the same with the trace backward inside (default neuron)
-template <int XL>
+template <int XL, bool SOFT = false>
 __global__ __launch_bounds__(256) void k_head_plif_bwd_mfma(
     const float4* __restrict__ g_z_out, const float4* __restrict__ g_v_out, const float4* __restrict__ v_out,
     const float4* __restrict__ v_prev, const uint32_t* __restrict__ z_prev, const float* __restrict__ leak,
@@ -1499,7 +1549,7 @@ __global__ __launch_bounds__(256) void k_head_plif_bwd_mfma(
   int nox[1][4];
   HeadBwdKeep keep;
   HeadBwdKeepPlif kp;
-  head_bwd_pass<true, 0, true, true, XL>(g_z_out, g_v_out, v_out, v_prev, z_prev, leak, thresh, npix, 1, EVF_ARCTAN, width, nullptr, g_v_prev,
+  head_bwd_pass<true, 0, true, true, XL, SOFT>(g_z_out, g_v_out, v_out, v_prev, z_prev, leak, thresh, npix, 1, EVF_ARCTAN, width, nullptr, g_v_prev,
                                      g_leak, g_thresh, x_in, Cin, H, W, slab, slab_acc, row_ld, none, none, nox, keep, true, pq, pm, gpc, &kp);
 }
 
@@ -1523,7 +1573,7 @@ struct HeadBwdWin {
   float width;
 };
 #define HEADBWD_NT 4  // trips of a block whose carried values fit registers (8 x 128 x 128 on 1024 blocks: 4)
-template <bool FAST, int NT, bool PLIF = false, int XL = 0>
+template <bool FAST, int NT, bool PLIF = false, int XL = 0, bool SOFT = false>
 __global__ __launch_bounds__(HEADBWD_LB) void k_head_bwd_win(HeadBwdWin a) {
   float4 gvc[NT ? NT : 1], voc[NT ? NT : 1], gpc[NT ? NT : 1];
   int xo[NT ? NT : 1][4];
@@ -1532,7 +1582,7 @@ __global__ __launch_bounds__(HEADBWD_LB) void k_head_bwd_win(HeadBwdWin a) {
   const int acc0 = a.p[0].slab_acc;  // (NT > 0: the sums of all passes are added to the slab once, by the first pass's rule)
   {
     const HeadBwdPass& q = a.p[0];
-    head_bwd_pass<FAST, NT, true, PLIF, XL>(q.g_z_out, q.g_v_out, q.v_out, q.v_prev, q.z_prev, a.leak, a.thresh, a.npix, a.hard_reset,
+    head_bwd_pass<FAST, NT, true, PLIF, XL, SOFT>(q.g_z_out, q.g_v_out, q.v_out, q.v_prev, q.z_prev, a.leak, a.thresh, a.npix, a.hard_reset,
                                         a.surrogate, a.width, nullptr, q.g_v_prev, a.g_leak, a.g_thresh, q.x_in, a.Cin, a.H, a.W, a.slab,
                                         NT > 0 ? acc0 : q.slab_acc, a.row_ld, gvc, voc, xo, keep, a.np == 1,
                                         HeadPlifPass{q.g_pt_out, q.pt_prev, q.P, q.g_pt_prev}, a.pm, gpc, &kp);
@@ -1540,7 +1590,7 @@ __global__ __launch_bounds__(HEADBWD_LB) void k_head_bwd_win(HeadBwdWin a) {
   for (int t = 1; t < a.np; ++t) {
     __syncthreads();  // (the pass's last reads of the reduction arrays before the next pass rewrites them)
     const HeadBwdPass& q = a.p[t];
-    head_bwd_pass<FAST, NT, false, PLIF, XL>(q.g_z_out, q.g_v_out, q.v_out, q.v_prev, q.z_prev, a.leak, a.thresh, a.npix, a.hard_reset,
+    head_bwd_pass<FAST, NT, false, PLIF, XL, SOFT>(q.g_z_out, q.g_v_out, q.v_out, q.v_prev, q.z_prev, a.leak, a.thresh, a.npix, a.hard_reset,
                                          a.surrogate, a.width, nullptr, q.g_v_prev, a.g_leak, a.g_thresh, q.x_in, a.Cin, a.H, a.W, a.slab,
                                          NT > 0 ? acc0 : q.slab_acc, a.row_ld, gvc, voc, xo, keep, t == a.np - 1,
                                          HeadPlifPass{q.g_pt_out, q.pt_prev, q.P, q.g_pt_prev}, a.pm, gpc, &kp);
@@ -1591,13 +1641,16 @@ static int head_bwd_go(const HdArgs& a, void* stream) {
   const int row_ld = a.accumulate >> 8;  // pitch of the per-block parameter-gradient rows (0: dense outputs, atomics)
   const int accumulate = a.accumulate & 1;
   if (a.P) {
-#define HEAD_PLIF_BWD(XL_)                                                                                                       \
-  hipLaunchKernelGGL(k_head_plif_bwd_mfma<XL_>, dim3(nblk), dim3(256), 0, EVF_STREAM(stream), (const float4*)a.g_z_out,           \
+#define HEAD_PLIF_BWD(...)                                                                                                       \
+  hipLaunchKernelGGL((k_head_plif_bwd_mfma<__VA_ARGS__>), dim3(nblk), dim3(256), 0, EVF_STREAM(stream), (const float4*)a.g_z_out,           \
                      (const float4*)a.g_v_out, (const float4*)a.v_out, (const float4*)a.v_prev, a.z_prev, a.leak, a.thresh, npix, \
                      a.act_width, (float4*)a.g_v_prev, a.g_leak, a.g_thresh, a.x_in, a.Cin, a.H, a.W, a.slab, accumulate, row_ld,  \
                      HeadPlifPass{(const float4*)a.g_pt_out, (const float4*)a.pt_prev, a.P, (float4*)a.g_pt_prev},               \
                      HeadPlifPrm{a.leak_pt, a.add_pt, a.g_leak_pt, a.g_add_pt})
-    if (((a.hard_reset >> 1) & 3) == 2) HEAD_PLIF_BWD(2);  // (bits 1-2: 1 an XLIF head, 2 an ALIF head)
+    const bool soft = (a.hard_reset & 6) && !(a.hard_reset & 1);  // (an XLIF / ALIF head with the soft reset)
+    if (soft && ((a.hard_reset >> 1) & 3) == 2) HEAD_PLIF_BWD(2, true);
+    else if (soft) HEAD_PLIF_BWD(1, true);
+    else if (((a.hard_reset >> 1) & 3) == 2) HEAD_PLIF_BWD(2);  // (bits 1-2: 1 an XLIF head, 2 an ALIF head)
     else if (a.hard_reset & 2) HEAD_PLIF_BWD(1);
     else HEAD_PLIF_BWD(0);
 #undef HEAD_PLIF_BWD
@@ -1703,7 +1756,14 @@ int evf_hd_defer_launch_window(int ctx, void* stream) {
 #define HEAD_BWD_WIN(FAST_, NT_) hipLaunchKernelGGL((k_head_bwd_win<FAST_, NT_>), dim3(nblk), dim3(256), 0, EVF_STREAM(stream), a)
       if (f.P) {  // PLIF (default neuron only: evf_head_plif_bwd_wgrad): three trips' carried values fit the registers
         const bool win3 = carry && trips <= 3 && (long)f.B * f.Cin * f.H * f.W < (1L << 31);
-        if (((f.hard_reset >> 1) & 3) == 2) {  // (bits 1-2: 2 an ALIF head, 1 an XLIF head)
+        const bool soft = (f.hard_reset & 6) && !(f.hard_reset & 1);  // (an XLIF / ALIF head with the soft reset)
+        if (soft && ((f.hard_reset >> 1) & 3) == 2) {
+          if (win3) hipLaunchKernelGGL((k_head_bwd_win<true, 3, true, 2, true>), dim3(nblk), dim3(256), 0, EVF_STREAM(stream), a);
+          else hipLaunchKernelGGL((k_head_bwd_win<true, 0, true, 2, true>), dim3(nblk), dim3(256), 0, EVF_STREAM(stream), a);
+        } else if (soft) {
+          if (win3) hipLaunchKernelGGL((k_head_bwd_win<true, 3, true, 1, true>), dim3(nblk), dim3(256), 0, EVF_STREAM(stream), a);
+          else hipLaunchKernelGGL((k_head_bwd_win<true, 0, true, 1, true>), dim3(nblk), dim3(256), 0, EVF_STREAM(stream), a);
+        } else if (((f.hard_reset >> 1) & 3) == 2) {  // (bits 1-2: 2 an ALIF head, 1 an XLIF head)
           if (win3) hipLaunchKernelGGL((k_head_bwd_win<true, 3, true, 2>), dim3(nblk), dim3(256), 0, EVF_STREAM(stream), a);
           else hipLaunchKernelGGL((k_head_bwd_win<true, 0, true, 2>), dim3(nblk), dim3(256), 0, EVF_STREAM(stream), a);
         } else if (f.hard_reset & 2) {
@@ -1778,7 +1838,8 @@ extern "C" int evf_head_plif_bwd_wgrad(const float* g_z_out, const float* g_v_ou
   if (!v_out || !x_in || !leak || !thresh || !g_v_prev || !g_leak || !g_thresh || !slab || B <= 0 || H <= 0 || W <= 0 ||
       Cin != 2 || !P || !leak_pt || !add_pt || !g_pt_prev || !g_leak_pt || !g_add_pt)
     return EVF_EINVAL;
-  if (!((hard_reset & 1) && surrogate == EVF_ARCTAN)) return EVF_ENOTSUP;  // (the two-call path serves the other neurons; bit 1: an XLIF head)
+  // (the two-call path serves the other neurons; bits 1-2: an XLIF / ALIF head -- served with either reset rule)
+  if (!(((hard_reset & 1) || (hard_reset & 6)) && surrogate == EVF_ARCTAN)) return EVF_ENOTSUP;
   const HdArgs a{g_z_out, g_v_out, v_out, v_prev, z_prev, x_in, leak, thresh, B, Cin, H, W, hard_reset, surrogate, act_width,
                  nullptr, g_v_prev, g_leak, g_thresh, slab, accumulate, g_pt_carry, pt_prev, P, leak_pt, add_pt, g_pt_prev,
                  g_leak_pt, g_add_pt};

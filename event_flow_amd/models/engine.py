@@ -181,13 +181,20 @@ class FireNetEngine:
         self._xl = self.kind == "xlif"
         self._al = self.kind == "alif"
         self._xf = 2 if self._xl else (4 if self._al else 0)
+        # ... with the soft reset (the cells' own default; models/model.py admits it under EVF_XLIF_SOFT_FUSED=1): bit 0 of the reset flag
+        # clear beside mode 1 / 2, bit 3 of the window entry points' `accumulate` (include/evflow.h) -- the same schedules, the kernels'
+        # soft-reset instantiations.  The opt-in is the ROUTING's (models/model.py, _xlif_fused_why): this constructor does not read the
+        # switch -- whoever builds an engine directly from all-soft XLIF / ALIF cells gets the soft kernels.
+        self._xsoft = (self._xl or self._al) and not cells[0].hard_reset
         for i, c in enumerate(cells):
             if c.kind not in ("lif", "plif", "xlif", "alif") or c.kind != self.kind:
                 raise NotImplementedError(f"{type(c).__name__}: LIF, PLIF, XLIF and ALIF cells are accelerated; there is no CPU fallback")
             if self._plif and precision != "bf16x3":
                 raise NotImplementedError("PLIF / XLIF / ALIF cells are implemented on the bf16x3 path only")
-            if c.kind in ("xlif", "alif") and not (c.hard_reset and c.activation == "arctanspike" and PLIF_TRACE_FUSED):
-                raise NotImplementedError("fused XLIF / ALIF cells: hard reset, arctan surrogate, trace backward inside the fused backward")
+            if c.kind in ("xlif", "alif") and not (bool(c.hard_reset) == bool(cells[0].hard_reset) and c.activation == "arctanspike"
+                                                   and PLIF_TRACE_FUSED):
+                raise NotImplementedError("fused XLIF / ALIF cells: one reset rule for all cells, arctan surrogate, trace backward inside "
+                                          "the fused backward")
             if c.hidden_size != C or c.kernel_size != 3 or c.stride != 1 or (i > 0 and c.input_size != C):
                 raise NotImplementedError("accelerated FireNet kernels need base_num_channels=32, kernel_size=3")
             if i == 0 and c.recurrent:
@@ -643,7 +650,7 @@ class FireNetEngine:
         return (HEAD_WIN and PLIF_TRACE_FUSED and PLIF_BOX_IN_DGRAD and TOP_FUSED and F32_DGRAD and PAIR_DGRAD and PARAM_ROWS
                 and self.__dict__.get("_bdefer_on", False) and win.rows is not None and n > 2 and not self.cells[n - 1].recurrent
                 and tape["x_in"].shape[1] == 2 and len(win.lm) < 16 and win.bwd_k == 0
-                and all(c.hard_reset and c.activation == "arctanspike" for c in self.cells))
+                and all((c.hard_reset or self._xsoft) and c.activation == "arctanspike" for c in self.cells))
 
     def _top_static(self, B, H, W):
         """The part of _top_wanted that depends on the network, the switches and the shape only (bench.py's accounting asks)."""
@@ -746,6 +753,8 @@ class FireNetEngine:
         rowp = lambda name: _lib.ptr(self._rowed(win, name)[0])  # noqa: E731
         row_ld = win.rows.shape[1]
         xf = self._xf  # (bits 1-2 of the reset / accumulate flag: XLIF / ALIF cells, include/evflow.h)
+        hr = 0 if self._xsoft else 1      # bit 0 of the one-pass entry points' reset flag
+        xw = xf | (8 if self._xsoft else 0)  # ... of the window entry points' accumulate: bit 3 = the soft reset
         for i in range(n - 1, 0, -1):
             c = self.cells[i]
             lay = [tp["layers"][i] for tp in tapes]  # (in_bits, v_prev, z_prev, v_out, z_out, in_bitsT, zT_prev, pt_prev, pt_out, P)
@@ -760,14 +769,14 @@ class FireNetEngine:
                           arr([l_[2] for l_ in lay]), arr([l_[5] for l_ in lay]), arr_n(gcur), arr_n(gsp), arr([l_[7] for l_ in lay]),
                           arr([l_[9] for l_ in lay]), arr(gPs), leak, thr, lpt, apt, B, H, W, width, None, None, rowp(f"{i}.leak"),
                           rowp(f"{i}.thresh"), rowp(f"{i}.leak_pt"), rowp(f"{i}.add_pt"), _lib.ptr(self._slab(kf, nsl, dev)),
-                          (1 if win.slab_init.get(kf) else 0) | xf | (row_ld << 8))
+                          (1 if win.slab_init.get(kf) else 0) | xw | (row_ld << 8))
                 win.slab_init[kf] = True
             elif not c.recurrent:  # feed-forward: all passes in one launch, the carries in registers
                 _lib.call("evf_plif_bwd_wgrad_window", T, arr([gz(i, s_) for s_ in range(T)]), arr([l_[3] for l_ in lay]),
                           arr([l_[1] for l_ in lay]), arr([l_[2] for l_ in lay]), arr([l_[5] for l_ in lay]), arr_n(gcur), arr_n(gsp),
                           arr([l_[7] for l_ in lay]), arr([l_[9] for l_ in lay]), arr(gPs), leak, thr, lpt, apt, B, H, W, width, None, None,
                           rowp(f"{i}.leak"), rowp(f"{i}.thresh"), rowp(f"{i}.leak_pt"), rowp(f"{i}.add_pt"),
-                          _lib.ptr(self._slab(kf, nsl, dev)), (1 if win.slab_init.get(kf) else 0) | xf | (row_ld << 8))
+                          _lib.ptr(self._slab(kf, nsl, dev)), (1 if win.slab_init.get(kf) else 0) | xw | (row_ld << 8))
                 win.slab_init[kf] = True
             if not c.recurrent and split:  # input gradients of all passes in one launch (the pooling's adjoint of dL/dP inside)
                 wts = [self._packed[(i, "ff", "b3t")]] * T
@@ -791,7 +800,7 @@ class FireNetEngine:
                 # (ALIF: gzr_i also takes the cell's g_zx -- read as the second part of dL/d(spikes), then written, by the same thread)
                 _lib.call("evf_plif_bwd_wgrad2", _lib.ptr(gz(i, s_)), _lib.ptr(gzr_i) if has_gzr else None, _lib.ptr(gv_i) if s_ else None,
                           _lib.ptr(v_out), _lib.ptr(v_prev), _lib.ptr(z_prev), _lib.ptr(in_bitsT), _lib.ptr(zT_prev) if use_rec else None,
-                          leak, thr, B, H, W, 1 | xf, SURROGATE_ID[c.activation], width, _lib.ptr(gcur[s_]), _lib.ptr(gsp[s_]), _lib.ptr(gv_i),
+                          leak, thr, B, H, W, hr | xf, SURROGATE_ID[c.activation], width, _lib.ptr(gcur[s_]), _lib.ptr(gsp[s_]), _lib.ptr(gv_i),
                           rowp(f"{i}.leak"), rowp(f"{i}.thresh"), _lib.ptr(self._slab(kf, nsl, dev)),
                           _lib.ptr(self._slab(kr, nsl, dev)) if use_rec else None, acc | (row_ld << 8),
                           _lib.ptr(gpt_i) if s_ else None, _lib.ptr(pt_prev), _lib.ptr(P_sav), lpt, apt, _lib.ptr(gpt_i),
@@ -835,7 +844,7 @@ class FireNetEngine:
                 raise _lib.EvflowError("evf_bwd_defer_slot failed")
             _lib.call("evf_head_plif_bwd_wgrad", _lib.ptr(gz(0, s_)), _lib.ptr(gv0) if s_ else None, _lib.ptr(v_out), _lib.ptr(v_prev),
                       _lib.ptr(z_prev), _lib.ptr(tapes[s_]["x_in"]), _lib.ptr(self._flat["0.leak"]), _lib.ptr(self._flat["0.thresh"]), B, 2, H, W,
-                      1 | xf, SURROGATE_ID[c.activation], self._act_width(0), _lib.ptr(gv0), rowp("0.leak"), rowp("0.thresh"),
+                      hr | xf, SURROGATE_ID[c.activation], self._act_width(0), _lib.ptr(gv0), rowp("0.leak"), rowp("0.thresh"),
                       _lib.ptr(self._slabs[key]), (1 if win.slab_init.get(key) else 0) | (row_ld << 8), _lib.ptr(gpt0) if s_ else None,
                       _lib.ptr(pt_prev), _lib.ptr(self._lm_buf(("gzx", 0), shp, dev) if self._al else P_sav),  # (ALIF: g_zx in the P slot)
                       _lib.ptr(self._flat["0.leak_pt"]), _lib.ptr(self._flat["0.add_pt"]), _lib.ptr(gpt0),
@@ -871,8 +880,8 @@ class FireNetEngine:
         # pass): a recording is open for them, the hidden cells' input gradients (pooling adjoint: not recordable) flush the rest
         # pass by pass, and evf_bwd_defer_flush runs the head's passes in ONE launch with the trace backward inside
         plif_hw = (self._plif and HEAD_WIN and PLIF_TRACE_FUSED and self.__dict__.get("_bdefer_on", False)
-                   and self.precision == "bf16x3" and n > 1 and tape["x_in"].shape[1] == 2 and self.cells[0].hard_reset
-                   and self.cells[0].activation == "arctanspike" and (top_fused or g_flow is None))
+                   and self.precision == "bf16x3" and n > 1 and tape["x_in"].shape[1] == 2
+                   and (self.cells[0].hard_reset or self._xsoft) and self.cells[0].activation == "arctanspike" and (top_fused or g_flow is None))
         if plif_hw:
             self._bdefer_slot(win, 0)
             if _lib.raw("evf_bwd_defer_hold_heads", 1) != 0:
@@ -912,7 +921,7 @@ class FireNetEngine:
             (leak_r, row_ld), (thr_r, _) = self._rowed(win, f"{i}.leak"), self._rowed(win, f"{i}.thresh")
             # PLIF: the trace backward rides in the fused backward (default neuron, pooling adjoint inside the input-gradient kernels)
             trace_fused = (plif and PLIF_TRACE_FUSED and PLIF_BOX_IN_DGRAD and i > 0 and self.precision == "bf16x3"
-                           and c.hard_reset and c.activation == "arctanspike")
+                           and (c.hard_reset or self._xsoft) and c.activation == "arctanspike")
             if (self._xl or self._al) and ((i > 0 and not trace_fused) or (i == 0 and tape["x_in"].shape[1] != 2)):
                 raise _lib.EvflowError("fused XLIF / ALIF cells need the trace backward inside the fused backward kernels (EVF_PLIF_TRACE_FUSED, "
                                        "EVF_PLIF_BOX=dgrad, a two-channel input); EVF_XLIF_FUSED=0 serves the network on the general path")
@@ -982,8 +991,8 @@ class FireNetEngine:
                     gpt_out = win.buf(win.gpt, 0)
                     _lib.call("evf_head_plif_bwd_wgrad", _lib.ptr(g_z), _lib.ptr(g_v), _lib.ptr(v_out), _lib.ptr(v_prev),
                               _lib.ptr(z_prev), _lib.ptr(tape["x_in"]), _lib.ptr(self._flat["0.leak"]),
-                              _lib.ptr(self._flat["0.thresh"]), B, 2, H, W, 1 | xf, SURROGATE_ID[c.activation], self._act_width(0),
-                              _lib.ptr(gv_out), _lib.ptr(leak_r), _lib.ptr(thr_r), _lib.ptr(self._slabs[key]),
+                              _lib.ptr(self._flat["0.thresh"]), B, 2, H, W, (0 if self._xsoft else 1) | xf, SURROGATE_ID[c.activation],
+                              self._act_width(0), _lib.ptr(gv_out), _lib.ptr(leak_r), _lib.ptr(thr_r), _lib.ptr(self._slabs[key]),
                               (1 if win.slab_init.get(key) else 0) | (row_ld << 8),
                               _lib.ptr(gpt_out if win.gpt_has[0] else None), _lib.ptr(pt_prev),
                               _lib.ptr(win.buf(win.gzr, 0) if self._al else P_sav),  # (ALIF: the g_zx buffer in the P slot, include/evflow.h)

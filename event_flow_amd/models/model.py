@@ -22,15 +22,23 @@ from .engine import FireNetEngine
 
 def _xlif_fused_why(cells, precision):
     """XLIF and ALIF cells ride on the PLIF kernels (threshold t0 + t1 * trace instead of the trace in the current; ALIF: the trace
-    driven by the cell's own previous spikes); their backward forms exist for the default neuron only (configs/train_SNN.yml: hard
-    reset, arctan surrogate), with the trace backward inside the fused backward kernels, a two-channel input and the bf16x3 forward.
+    driven by the cell's own previous spikes); their backward forms exist for the arctan surrogate with the hard reset (configs/
+    train_SNN.yml) and -- opt-in, EVF_XLIF_SOFT_FUSED=1 -- with the cells' own default, the soft reset - z * (t0 + t1 * trace before the
+    pass); one reset rule for all seven cells, the trace backward inside the fused backward kernels, a two-channel input and the
+    bf16x3 forward.  Both switches are read at call time.
     -> "" when the fused engine serves these cells, else the reason the general path does (EVF_XLIF_FUSED=0: always)."""
     from . import engine
 
     if os.environ.get("EVF_XLIF_FUSED", "1") == "0":
         return "EVF_XLIF_FUSED=0"
-    if not all(c.hard_reset and c.activation == "arctanspike" for c in cells):
-        return "XLIF / ALIF cells with the soft reset or another surrogate than arctanspike (their fused kernels: hard reset, arctan)"
+    if os.environ.get("EVF_XLIF_SOFT_FUSED", "0") != "1":
+        if not all(c.hard_reset and c.activation == "arctanspike" for c in cells):
+            return "XLIF / ALIF cells with the soft reset or another surrogate than arctanspike (their fused kernels: hard reset, arctan)"
+    else:  # opt-in: the cells' own default reset on the fused engine, one rule for all seven cells
+        if not all(c.activation == "arctanspike" for c in cells):
+            return "XLIF / ALIF cells with another surrogate than arctanspike (their fused kernels: arctan)"
+        if len({bool(c.hard_reset) for c in cells}) > 1:
+            return "XLIF / ALIF cells with mixed reset rules, hard and soft reset in one network (their fused kernels: one rule for all cells)"
     if cells[0].input_size != 2:
         return f"XLIF / ALIF cells behind a {cells[0].input_size}-channel input (their fused head kernels: two channels)"
     if not engine.PLIF_TRACE_FUSED:
@@ -124,7 +132,8 @@ class FireNet(BaseModel):
 
                 print(f"[event_flow_amd] {type(self).__name__}: general path (one fused conv + neuron kernel per cell, "
                       f"models/hip_ops.py) -- {self.compute_path[1]}; the recorded 32-channel window kernels (models/engine.py) "
-                      "serve LIF / PLIF FireNets (and XLIF / ALIF ones with the hard reset, the arctan surrogate and a two-channel input) with base_num_channels=32, "
+                      "serve LIF / PLIF FireNets (and XLIF / ALIF ones with the arctan surrogate, a two-channel input and the hard reset -- or, with "
+                      "EVF_XLIF_SOFT_FUSED=1, the soft reset in all cells) with base_num_channels=32, "
                       "kernel_size=3, no residual / weight / group norm",
                       file=sys.stderr)
         return self._use_fused

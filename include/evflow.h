@@ -398,9 +398,17 @@ int evf_conv_dgrad_b3_f32_pair(const float* g_cur, const void* wT_b3, float* g_x
  * (current = ff (+rec)).  Bits 1-2 of `hard_reset` (evf_conv_plif_fwd_b3[_pred], evf_head_plif_fwd, evf_plif_bwd_wgrad2 / _top,
  * evf_head_plif_bwd_wgrad: pass `hard_reset | 2`) or of `accumulate` (evf_plif_bwd_wgrad_window[_top]: `accumulate | 2`) select
  * them; `thresh` / `g_thresh` then carry t0 and its gradient, `add_pt` / `g_add_pt` carry t1 and its gradient (no sigmoid:
- * the clamp's sub-gradient).  Backward forms: hard reset + arctan surrogate only, like the PLIF ones; the forward also takes
- * the soft reset (v' -= z * (t0 + t1 * pt)) cell by cell, except for the head (EVF_ENOTSUP).  evf_plif_trace_bwd has no XLIF
- * form (the trace backward of an XLIF cell lives in the fused backward kernels).
+ * the clamp's sub-gradient).  Backward forms: the arctan surrogate only, like the PLIF ones.
+ * The soft reset of XLIF / ALIF cells (the reference constructors' default: v' = v * lam + (1 - lam) * cur - z * (t0 + t1 * pt),
+ * pt = the trace BEFORE the pass, z detached, t0 / t1 / pt not) is served by every one of these entry points: bit 0 of `hard_reset`
+ * clear together with mode 1 or 2 in bits 1-2 -- evf_conv_plif_fwd_b3[_pred] (one cell and recorded: diagonals and chains),
+ * evf_head_plif_fwd (one pass and recorded window), evf_plif_bwd_wgrad2 / _top, evf_head_plif_bwd_wgrad (one pass and recorded
+ * window); evf_plif_bwd_wgrad_window[_top], which have no `hard_reset`, take it as bit 3 of `accumulate` (`accumulate | 8`, beside
+ * mode 1 or 2 in bits 1-2).  One reset rule per recorded launch (cells of both rules under one forward index run cell by cell).  The
+ * backward sends -gv * z to t0, -gv * z * pt to t1 and -gv * z * t1 to the trace carry of the pass before (gv = dL/dv' + dL/dz * sg),
+ * and dL/dv has no (1 - z) factor.  A PLIF cell proper (mode 0) with the soft reset stays EVF_ENOTSUP in every fused backward form
+ * (evf_lif_bwd_wgrad* + evf_plif_trace_bwd serve it).  evf_plif_trace_bwd has no XLIF form (the trace backward of an XLIF cell
+ * lives in the fused backward kernels).
  *
  * ALIF cells (:230-334, :660-768): the value 2 in those two bits (`hard_reset | 4`, `accumulate | 4`).  The XLIF arithmetic with
  * the trace t' = t * s(leak_t) + (1 - s(leak_t)) * z driven by the cell's OWN previous spikes z (`leak_pt` = leak_t, `pt_*` = the
