@@ -33,6 +33,11 @@ SIGNATURES = {
     "evf_cm_loss_ws": [I, I, I, I, I],
     "evf_cm_loss_fwd": [P, P, P, P, P, I, I, I, I, I, I, F, F, I, P, P, P, P, P, P],
     "evf_cm_loss_bwd": [P, P, P, P, P, I, I, I, I, I, I, F, F, I, P, P, P, P, P, P],
+    # the deterministic form (exact, order-independent sums): ws mandatory, followed by its size in floats
+    "evf_cm_loss_ws_det": [I, I, I, I, I],
+    "evf_cm_loss_fwd_det": [P, P, P, P, P, I, I, I, I, I, I, F, F, I, P, P, P, P, P, L, P],
+    "evf_cm_loss_bwd_ws_det": [I, I, I, I, I, I, I],
+    "evf_cm_loss_bwd_det": [P, P, P, P, P, I, I, I, I, I, I, F, F, I, P, P, P, P, P, P, L, P],
     "evf_image_variance": [P, I, I, P, P],
     "evf_avg_ts_ratio": [P, I, I, F, P, P],
     "evf_aee": [P, P, P, P, I, I, I, F, P, P],
@@ -172,10 +177,25 @@ NETWORK_SIGNATURES = {
     "evf_gru_out_bwd": [P, P, P, P, L, P, P, P, P],
     "evf_gru_gates_bwd": [P, P, P, L, P, P, P],
 }
-RESTYPES = {"evf_head1x1_ws": ctypes.c_int64, "evf_comm_last_error": ctypes.c_char_p, "evf_conv2d_packed_size": ctypes.c_int64, "evf_conv2d_b3_packed_size": ctypes.c_int64, "evf_conv2d_b3_ws": ctypes.c_int64, "evf_conv2d_wgrad_ws": ctypes.c_int64, "evf_cm_loss_ws": ctypes.c_int64}
+RESTYPES = {"evf_head1x1_ws": ctypes.c_int64, "evf_comm_last_error": ctypes.c_char_p, "evf_conv2d_packed_size": ctypes.c_int64, "evf_conv2d_b3_packed_size": ctypes.c_int64, "evf_conv2d_b3_ws": ctypes.c_int64, "evf_conv2d_wgrad_ws": ctypes.c_int64, "evf_cm_loss_ws": ctypes.c_int64, "evf_cm_loss_ws_det": ctypes.c_int64, "evf_cm_loss_bwd_ws_det": ctypes.c_int64}
 SIGNATURES.update(NETWORK_SIGNATURES)
 
 _lib = None
+
+# Deterministic mode (EVF_DETERMINISTIC=1 at import, set_deterministic): the contrast-maximisation loss goes through
+# evf_cm_loss_fwd_det / evf_cm_loss_bwd_det (exact, order-independent sums) instead of the float atomics.  A switch of this
+# module, not of the library: the C ABI has one entry point per form.
+_deterministic = os.environ.get("EVF_DETERMINISTIC", "0") == "1"
+
+
+def set_deterministic(on):
+    """Route the contrast-maximisation loss through its deterministic entry points (True) or the default ones (False)."""
+    global _deterministic
+    _deterministic = bool(on)
+
+
+def deterministic():
+    return _deterministic
 
 
 class EvflowError(RuntimeError):

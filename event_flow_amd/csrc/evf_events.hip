@@ -1222,6 +1222,207 @@ extern "C" int evf_cm_loss_fwd(const float* flow, const float* ev, const float* 
   return evf_status();
 }
 
+// ---- the deterministic form (evf_cm_loss_fwd_det): exact, order-independent image sums -----------------------------------
+// The float atomics above make a pixel's sum depend on the order in which lanes, waves and blocks deliver its terms.  Here every
+// term is scaled by 2^k (exact), rounded ONCE to a 64-bit integer and added with the LDS integer atomic: integer addition is
+// associative, so the sum is a function of the SET of terms.  k depends on the shape of the call alone (cm_det_scale_log2), never
+// on its data.  The stripes hold 8-byte slots, i.e. half the rows of k_cm_splat_lds; the pre-pass and the scan are that kernel's.
+// A term is |wt * pol| <= 1 or |wt * tau * pol| <= P for polarity weights in [-1, 1] and event times in [0, 1] within a pass, a
+// pixel receives at most one tap of each of the M events: |sum * 2^k| <= M * P * 2^k < 2^62.
+static int cm_det_scale_log2(int M, int P) {  // the largest k with M * max(P, 1) * 2^k < 2^62
+  const unsigned long long n = (unsigned long long)M * (unsigned long long)(P > 1 ? P : 1);
+  return 61 - (63 - __builtin_clzll(n));
+}
+#define CM_DET_MIN_LOG2 32  // fewer fraction bits than this: refused (M * P >= 2^30)
+static int cm_det_rows(int S, int B, int H, int W) {
+  int rows = 4096 / W;  // 4 planes x rows x W 64-bit slots <= 128 KiB of LDS
+  if (rows > H) rows = H;
+  while (rows > 8 && (long)S * B * 2 * evf_cdiv(H, rows) < 512) rows >>= 1;  // (the rule of cm_lds_rows)
+  return rows;
+}
+
+// k_cm_pre with the per-stripe statistics slots of k_cm_splat_det to clear instead of `stats` (the pre-warp blocks share the work)
+__global__ __launch_bounds__(256) void k_cm_pre_det(const float* __restrict__ flow, const float4* __restrict__ ev,
+                                                    const float2* __restrict__ pol, const int32_t* __restrict__ ev_pass,
+                                                    const float* __restrict__ mask, int S, int Pm, int Pk, int P, int B, int M, int H,
+                                                    int W, float Sc, int use_mask, int with_dt, float4* __restrict__ warp,
+                                                    float* __restrict__ tabs, float* __restrict__ ys, float* __restrict__ part,
+                                                    float* __restrict__ slots, int nslots, unsigned* __restrict__ ticket, int nbw) {
+  __shared__ float red[16];
+  const int bid = blockIdx.x;
+  if (bid < nbw * S) {
+    for (long i = (long)bid * blockDim.x + threadIdx.x; i < nslots; i += (long)nbw * S * blockDim.x) slots[i] = 0.f;
+    if (bid == 0 && threadIdx.x == 0) ticket[0] = 0u;
+    cm_prewarp_body(bid % nbw, bid / nbw, flow, ev, pol, ev_pass, S, Pm, P, B, M, H, W, Sc, warp, tabs, ys);
+    return;
+  }
+  const int sb = bid - nbw * S, gx = (H + SM_ROWS - 1) / SM_ROWS;
+  cm_smooth_body(sb % gx, sb / gx, gx, red, flow, mask, Pm, Pk, B, H, W, use_mask, with_dt, part);
+}
+
+__global__ __launch_bounds__(1024) void k_cm_splat_det(const float4* __restrict__ warp, const float* __restrict__ tabs,
+                                                       const float* __restrict__ ys, int B, int M, int H, int W, int rows, float P,
+                                                       int k2, float* __restrict__ images, float* __restrict__ slots, CmFin fin) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  unsigned long long* img = (unsigned long long*)smem_raw;  // [4][rows*W] two's complement: I_pos, I_neg, TS_pos, TS_neg of this direction
+  const int sbd = blockIdx.y, d = sbd & 1, b = (sbd >> 1) % B;
+  const int r0 = blockIdx.x * rows, nr = min(rows, H - r0), plane = rows * W;
+  for (int q = threadIdx.x; q < 4 * plane; q += blockDim.x) img[q] = 0ull;
+  __syncthreads();
+  const float4* __restrict__ wp = warp + (long)sbd * M;
+  const float* __restrict__ tb = tabs + (long)b * M;
+  const float lo = (float)r0, hi = (float)(r0 + nr), fW = (float)W;
+  auto fix = [&](float v) { return (unsigned long long)__float2ll_rn(ldexpf(v, k2)); };  // (ldexpf: an exact scaling)
+  auto one = [&](const float4 w4, const float t) {  // (the weights and products of k_cm_splat_lds, term for term)
+    const float tau = d ? P - t : t;
+    const float cy[2] = {floorf(w4.x), floorf(w4.x + 1.0f)};
+    const float cx[2] = {floorf(w4.y), floorf(w4.y + 1.0f)};
+    float ay[2], ax[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      ay[k] = fmaxf(0.f, 1.0f - fabsf(w4.x - cy[k]));
+      ax[k] = fmaxf(0.f, 1.0f - fabsf(w4.y - cx[k]));
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        if (!(cy[j] >= lo && cy[j] < hi && cx[i] >= 0.f && cx[i] < fW)) continue;  // other stripes / outside (NaN too)
+        const float wt = ay[j] * ax[i];
+        if (wt == 0.f) continue;
+        unsigned long long* px = img + ((int)cy[j] - r0) * W + (int)cx[i];
+        const float wtau = wt * tau;
+        const float v0 = wt * w4.z, v1 = wt * w4.w, u0 = wtau * w4.z, u1 = wtau * w4.w;
+        if (v0 != 0.f) atomicAdd(px, fix(v0));
+        if (v1 != 0.f) atomicAdd(px + plane, fix(v1));
+        if (u0 != 0.f) atomicAdd(px + 2 * plane, fix(u0));
+        if (u1 != 0.f) atomicAdd(px + 3 * plane, fix(u1));
+      }
+  };
+  // the scan of k_cm_splat_lds: the warped row alone decides, the accepted records are fetched CM_NB at a time
+  const float* __restrict__ yp = ys + (long)sbd * M;
+  auto mine = [&](float y) {
+    const float c0 = floorf(y), c1 = floorf(y + 1.0f);
+    return (c0 >= lo && c0 < hi) || (c1 >= lo && c1 < hi);
+  };
+  for (int e0 = threadIdx.x; e0 < M; e0 += CM_CH * (int)blockDim.x) {
+    float y[CM_CH];
+#pragma unroll
+    for (int k = 0; k < CM_CH; ++k) y[k] = yp[min(e0 + k * (int)blockDim.x, M - 1)];
+    unsigned acc = 0u;
+#pragma unroll
+    for (int k = 0; k < CM_CH; ++k)
+      if (e0 + k * (int)blockDim.x < M && mine(y[k])) acc |= 1u << k;
+    while (__builtin_amdgcn_ballot_w64(acc != 0u) != 0ull) {
+      int idx[CM_NB];
+      bool ok[CM_NB];
+#pragma unroll
+      for (int j = 0; j < CM_NB; ++j) {
+        ok[j] = acc != 0u;
+        const int k = ok[j] ? __builtin_ctz(acc) : 0;
+        acc &= acc - 1u;
+        idx[j] = min(e0 + k * (int)blockDim.x, M - 1);
+      }
+      float4 w4[CM_NB];
+      float tt[CM_NB];
+#pragma unroll
+      for (int j = 0; j < CM_NB; ++j) w4[j] = wp[idx[j]], tt[j] = tb[idx[j]];
+#pragma unroll
+      for (int j = 0; j < CM_NB; ++j)
+        if (ok[j]) one(w4[j], tt[j]);
+    }
+  }
+  __syncthreads();
+  // write-out: every sum converted ONCE, (float)sum * 2^-k, into the layout of k_cm_splat_lds; the statistics from the same floats
+  const long HW = (long)H * W;
+  float* o = images + ((long)(sbd >> 1) * 8 + d * 4) * HW + (long)r0 * W;
+  const int n = nr * W;
+  __shared__ float red[16];
+  __shared__ int s_last;
+  float sq = 0.f, nz = 0.f;
+  for (int p = threadIdx.x; p < n; p += blockDim.x) {
+    const float ip = ldexpf(__ll2float_rn((long long)img[p]), -k2), in = ldexpf(__ll2float_rn((long long)img[plane + p]), -k2);
+    const float tp = ldexpf(__ll2float_rn((long long)img[2 * plane + p]), -k2), tn = ldexpf(__ll2float_rn((long long)img[3 * plane + p]), -k2);
+    o[p] = ip, o[HW + p] = in, o[2 * HW + p] = tp, o[3 * HW + p] = tn;
+    const float ap = tp / (ip + 1e-9f) / P;  // loss/flow.py:212-215
+    const float an = tn / (in + 1e-9f) / P;
+    sq += ap * ap + an * an;
+    nz += (ip + in > 0.f) ? 1.f : 0.f;
+  }
+  sq = evf_block_sum(sq, red);  // (fixed order: the butterfly of the wave, then the waves by index)
+  nz = evf_block_sum(nz, red);
+  if (threadIdx.x == 0) {
+    // One slot per (scale, sample, direction, stripe), zeroed by k_cm_pre_det: this block is its only writer, 0 + x is exact and has
+    // no order.  Device-scope atomics all the same, for the memory-model argument of k_cm_splat_lds: performed at the memory side,
+    // complete at the workgroup-scope release, read by the last block with device-scope loads -- no agent-scope fence.
+    float* sl = slots + ((long)sbd * gridDim.x + blockIdx.x) * 2;
+    evf_atomic_add(sl, sq);
+    evf_atomic_add(sl + 1, nz);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    const unsigned t = __hip_atomic_fetch_add(fin.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = t == gridDim.x * gridDim.y - 1;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  // the last block: the stripes' parts in STRIPE INDEX order into `stats`, then the loss (cm_finalize_body: smoothness partials and
+  // statistics by thread-strided loops and evf_block_sum, the scales in sequence on thread 0 -- a fixed order as well)
+  const int nst = gridDim.x;
+  for (int i = threadIdx.x; i < fin.S * B * 2; i += blockDim.x) {
+    float a = 0.f, c = 0.f;
+    for (int j = 0; j < nst; ++j) {
+      const unsigned* sl = (const unsigned*)(slots + ((long)i * nst + j) * 2);
+      a += __uint_as_float(__hip_atomic_load(sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      c += __uint_as_float(__hip_atomic_load(sl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    }
+    __hip_atomic_store((unsigned*)(fin.stats + 2 * i), __float_as_uint(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store((unsigned*)(fin.stats + 2 * i + 1), __float_as_uint(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();  // (cm_finalize_body reads `stats` with device-scope loads, other threads of this block than the writers)
+  cm_finalize_body(red, fin.stats, fin.part, fin.S, B, fin.Pm, fin.nblk_per_scale, fin.weight, fin.comps, fin.loss_scaling, fin.loss);
+}
+
+// floats of scratch of evf_cm_loss_fwd_det: what evf_cm_loss_ws counts, and two statistics slots per (scale, sample, direction, stripe)
+extern "C" int64_t evf_cm_loss_ws_det(int S, int B, int M, int H, int W) {
+  if (S <= 0 || B <= 0 || M <= 0 || H <= 1 || W <= 1 || W > 2048 || cm_det_scale_log2(M, 1) < CM_DET_MIN_LOG2) return 0;
+  const int nst = evf_cdiv(H, cm_det_rows(S, B, H, W));
+  return (int64_t)S * B * 2 * M * 4 + (int64_t)B * M + 4 + (int64_t)S * B * 2 * M + (int64_t)S * B * 2 * nst * 2;
+}
+
+extern "C" int evf_cm_loss_fwd_det(const float* flow, const float* ev, const float* pol, const int32_t* ev_pass,
+                                   const float* mask, int S, int P, int B, int M, int H, int W, float flow_scaling,
+                                   float regul_weight, int flags, float* images, float* stats, float* smooth_part,
+                                   float* loss, float* ws, int64_t ws_floats, void* stream) {
+  if (!cm_args_ok(flow, ev, pol, ev_pass, mask, S, P, B, M, H, W, flags) || !images || !stats || !smooth_part || !loss || !ws)
+    return EVF_EINVAL;
+  if (W > 2048 || cm_det_scale_log2(M, P) < CM_DET_MIN_LOG2) return EVF_ENOTSUP;
+  if (ws_floats < evf_cm_loss_ws_det(S, B, M, H, W)) return EVF_EINVAL;
+  hipStream_t st = EVF_STREAM(stream);
+  const int overwrite = (flags & 2) ? 1 : 0;
+  const int Pm = overwrite ? 1 : P, Pk = Pm;
+  const int srows = evf_cdiv(H, SM_ROWS);
+  float4* warp = (float4*)ws;
+  float* tabs = ws + (size_t)S * B * 2 * M * 4;
+  unsigned* ticket = (unsigned*)(tabs + (size_t)B * M);
+  float* ys = tabs + (size_t)B * M + 4;
+  float* slots = ys + (size_t)S * B * 2 * M;
+  const int rows = cm_det_rows(S, B, H, W), nst = evf_cdiv(H, rows);
+  const size_t lds = (size_t)4 * rows * W * sizeof(unsigned long long);
+  static size_t lds_set = 0;
+  if (lds > lds_set) {
+    (void)hipFuncSetAttribute((const void*)k_cm_splat_det, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    lds_set = lds;
+  }
+  // always the two merged launches, whatever the event count (evf_cm_merge and the caller's size threshold do not apply)
+  const int nbw = evf_cdiv((long)B * M, 256);
+  hipLaunchKernelGGL(k_cm_pre_det, dim3(nbw * S + srows * S * Pm * B), dim3(256), 0, st, flow, (const float4*)ev, (const float2*)pol,
+                     ev_pass, mask, S, Pm, Pk, P, B, M, H, W, flow_scaling, flags & 1, overwrite ? 0 : 1, warp, tabs, ys, smooth_part,
+                     slots, S * B * 2 * nst * 2, ticket, nbw);
+  const CmFin fin{stats, ticket, smooth_part, loss, S, Pm, srows * Pm * B, overwrite ? 4 : 5, (flags & 4) ? 1 : 0, regul_weight};
+  hipLaunchKernelGGL(k_cm_splat_det, dim3(nst, S * B * 2), dim3(1024), lds, st, (const float4*)warp, tabs, ys, B, M, H, W, rows,
+                     (float)P, cm_det_scale_log2(M, P), images, slots, fin);
+  return evf_status();
+}
+
 // --------------------------------------------------------------------------
 // contrast-maximisation loss, backward
 // --------------------------------------------------------------------------
@@ -1578,6 +1779,174 @@ extern "C" int evf_cm_loss_bwd(const float* flow, const float* ev, const float* 
   }
   hipLaunchKernelGGL(k_cm_event_bwd, dim3(8 * evf_cdiv((long)B * M, 256 * 8), S), dim3(256), 0, st, flow, (const float4*)ev,
                      (const float2*)pol, ev_pass, S, Pm, P, B, M, H, W, flow_scaling, gimages, dflow);
+  return evf_status();
+}
+
+// ---- the deterministic form (evf_cm_loss_bwd_det): two kernels instead of one ----------------------------------------------
+// k_cm_event_grad: the arithmetic of k_cm_event_bwd, one event per thread on full waves -- the twelve divergent gathers per event
+// happen once --, the event's (dL/dflow_x, dL/dflow_y) STORED per (scale, sample, event) instead of added anywhere, and the
+// largest magnitude of each dL/dflow map (scale, map, sample) kept by an integer atomicMax on the floats' bit patterns: for
+// non-negative floats the order of the bit patterns is the order of the values (a NaN's pattern lies above infinity's), and a
+// maximum does not depend on the order of its operands.
+__global__ __launch_bounds__(256) void k_cm_event_grad(const float* __restrict__ flow, const float4* __restrict__ ev,
+                                                       const float2* __restrict__ pol, const int32_t* __restrict__ ev_pass, int S,
+                                                       int Pm, int P, int B, int M, int H, int W, float Sc,
+                                                       const float* __restrict__ gim, float2* __restrict__ gev,
+                                                       unsigned* __restrict__ gmax) {
+  const long vb = (long)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);  // (k_cm_event_bwd: an XCD walks a contiguous eighth)
+  const long i0 = vb * blockDim.x + threadIdx.x;
+  const bool live = i0 < (long)B * M;
+  const long i = live ? i0 : (long)B * M - 1;  // (the tail lanes repeat the last event: full waves below, a maximum does not mind)
+  const int s = blockIdx.y;
+  const int b = (int)(i / M), e = (int)(i - (long)b * M);
+  const float4 q = ev[i];
+  const int pass = ev_pass[e];
+  const float t = q.x + (float)pass;
+  const float2 pm = pol[i];
+  const long HW = (long)H * W;
+  const int map = Pm == 1 ? 0 : pass;
+  float fy, fx;
+  evf_event_flow(flow + (long)s * Pm * B * 2 * HW, map, B, b, HW, q.y, q.z, W, fy, fx);
+  const float4* g = (const float4*)(gim + ((long)s * B + b) * 8 * HW);
+  const float maxts = (float)P;
+  float gfy = 0.f, gfx = 0.f;
+  {
+    float gwy = 0.f, gwx = 0.f;
+    evf_dir_grad(evf_warp(t, q.y, q.z, fy, fx, maxts, Sc), H, W, pm.x, pm.y, t, g, gwy, gwx);
+    const float k = (maxts - t) * Sc;  // d warped / d flow
+    gfy += gwy * k;
+    gfx += gwx * k;
+  }
+  {
+    float gwy = 0.f, gwx = 0.f;
+    evf_dir_grad(evf_warp(t, q.y, q.z, fy, fx, 0.f, Sc), H, W, pm.x, pm.y, maxts - t, g + HW, gwy, gwx);
+    const float k = (0.f - t) * Sc;
+    gfy += gwy * k;
+    gfx += gwx * k;
+  }
+  if (live) gev[(long)s * B * M + i] = make_float2(gfx, gfy);
+  unsigned bits = max(__float_as_uint(fabsf(gfx)), __float_as_uint(fabsf(gfy)));
+  const int key = map * B + b;
+  unsigned* mx = gmax + (long)s * Pm * B + key;
+  if (__builtin_amdgcn_ballot_w64(key != __builtin_amdgcn_readfirstlane(key)) == 0ull) {  // one map for the whole wave: one atomic
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bits = max(bits, (unsigned)__shfl_xor((int)bits, o, 64));
+    if ((threadIdx.x & 63) == 0 && bits) atomicMax(mx, bits);
+  } else if (bits) {
+    atomicMax(mx, bits);
+  }
+}
+
+// k_cm_event_sum_det: one block per (scale, map, sample, stripe of rows) as in k_cm_event_bwd_lds.  The block passes over the
+// sample's events by source pixel and pass and adds the stored gradients of its own as 64-bit fixed point, __float2ll_rn(g * 2^e),
+// with the LDS integer atomic: exact and order-independent.  No queue: the expensive part of an event is done, the scan
+// accumulates directly.  e comes, in integer arithmetic, from the exponent field E of the map's maximum and L = ceil(log2 M):
+// |g| < 2^(max(E,1) - 126), at most M <= 2^L events per pixel, so with e = 187 - L - max(E,1) every |sum * 2^e| <= 2^61.  A
+// function of the SET of events.  A map whose maximum is 0 has nothing to add; one whose maximum is not finite is summed in
+// floats (the pixels that receive a non-finite term come out non-finite; their bits, and the order, are not specified).
+#define CMD_THREADS 512
+__global__ __launch_bounds__(CMD_THREADS) void k_cm_event_sum_det(const float4* __restrict__ ev, const int32_t* __restrict__ ev_pass,
+                                                                   const float2* __restrict__ gev, const unsigned* __restrict__ gmax,
+                                                                   int S, int Pm, int B, int M, int H, int W, int rows, int L,
+                                                                   float* __restrict__ dflow) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int smb = blockIdx.x, b = smb % B, map = (smb / B) % Pm, s = smb / (B * Pm);
+  const unsigned mx = gmax[smb];
+  if (mx == 0u) return;  // (block-uniform)
+  const int E = (int)((mx >> 23) & 0xffu);
+  const int r0 = blockIdx.y * rows, nr = min(rows, H - r0), plane = rows * W;
+  const long HW = (long)H * W;
+  const long lo = (long)r0 * W, hi = (long)(r0 + nr) * W;
+  const float* __restrict__ evf = (const float*)(ev + (long)b * M);
+  const float2* __restrict__ g = gev + ((long)s * B + b) * M;
+  float* d = dflow + (((long)s * Pm + map) * B + b) * 2 * HW + lo;
+  const int n = nr * W;
+  if (E == 255) {
+    float* acc = (float*)smem_raw;  // [2][rows * W]
+    for (int q = threadIdx.x; q < 2 * plane; q += CMD_THREADS) acc[q] = 0.f;
+    __syncthreads();
+    for (int e = threadIdx.x; e < M; e += CMD_THREADS) {
+      const long lin = (long)(evf[4 * (long)e + 1] * (float)W + evf[4 * (long)e + 2]);
+      if ((Pm != 1 && ev_pass[e] != map) || !(lin >= lo && lin < hi)) continue;
+      const float2 v = g[e];
+      if (v.x != 0.f) atomicAdd(acc + (int)(lin - lo), v.x);
+      if (v.y != 0.f) atomicAdd(acc + plane + (int)(lin - lo), v.y);
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < 2 * n; q += CMD_THREADS) {
+      const int c = q >= n, r = q - c * n;
+      d[(long)c * HW + r] += acc[c * plane + r];
+    }
+    return;
+  }
+  unsigned long long* acc = (unsigned long long*)smem_raw;  // [2][rows * W] two's complement: x component, y component
+  const int e2 = 187 - L - (E > 1 ? E : 1);
+  for (int q = threadIdx.x; q < 2 * plane; q += CMD_THREADS) acc[q] = 0ull;
+  __syncthreads();
+  for (int e = threadIdx.x; e < M; e += CMD_THREADS) {
+    const long lin = (long)(evf[4 * (long)e + 1] * (float)W + evf[4 * (long)e + 2]);  // flow_idx (loss/flow.py:65-67), as evf_event_flow
+    if ((Pm != 1 && ev_pass[e] != map) || !(lin >= lo && lin < hi)) continue;  // (NaN coordinates: lin is not in the stripe)
+    const float2 v = g[e];
+    if (v.x != 0.f) atomicAdd(acc + (int)(lin - lo), (unsigned long long)__float2ll_rn(ldexpf(v.x, e2)));
+    if (v.y != 0.f) atomicAdd(acc + plane + (int)(lin - lo), (unsigned long long)__float2ll_rn(ldexpf(v.y, e2)));
+  }
+  __syncthreads();
+  // converted once and ADDED to the smoothness gradient k_cm_bwd_pre stored (one owner per pixel: plain loads and stores)
+  for (int q = threadIdx.x; q < 2 * n; q += CMD_THREADS) {
+    const int c = q >= n, r = q - c * n;
+    d[(long)c * HW + r] += ldexpf(__ll2float_rn((long long)acc[c * plane + r]), -e2);
+  }
+}
+
+static int cm_det_bwd_rows(int S, int Pm, int B, int H, int W) {
+  int rows = 4096 / W;  // 2 components x rows x W 64-bit slots <= 64 KiB of LDS
+  if (rows > H) rows = H;
+  while (rows > 8 && (long)S * Pm * B * evf_cdiv(H, rows) < 512) rows >>= 1;  // two blocks per CU at least
+  return rows;
+}
+
+// floats of scratch of evf_cm_loss_bwd_det: the events' gradients [S][B][M][2] and one maximum per dL/dflow map [S][Pm][B]
+extern "C" int64_t evf_cm_loss_bwd_ws_det(int S, int P, int B, int M, int H, int W, int flags) {
+  if (S <= 0 || P <= 0 || B <= 0 || M <= 0 || H <= 1 || W <= 1 || W > 2048 || cm_det_scale_log2(M, P) < CM_DET_MIN_LOG2) return 0;
+  const int Pm = (flags & 2) ? 1 : P;
+  return (int64_t)S * B * M * 2 + (((int64_t)S * Pm * B + 3) & ~(int64_t)3);
+}
+
+extern "C" int evf_cm_loss_bwd_det(const float* flow, const float* ev, const float* pol, const int32_t* ev_pass,
+                                   const float* mask, int S, int P, int B, int M, int H, int W, float flow_scaling,
+                                   float regul_weight, int flags, const float* images, const float* stats,
+                                   const float* grad_out, float* gimages, float* dflow, float* ws, int64_t ws_floats,
+                                   void* stream) {
+  if (!cm_args_ok(flow, ev, pol, ev_pass, mask, S, P, B, M, H, W, flags) || !images || !stats || !grad_out ||
+      !gimages || !dflow || !ws)
+    return EVF_EINVAL;
+  if (W > 2048 || cm_det_scale_log2(M, P) < CM_DET_MIN_LOG2) return EVF_ENOTSUP;
+  if (ws_floats < evf_cm_loss_bwd_ws_det(S, P, B, M, H, W, flags)) return EVF_EINVAL;
+  hipStream_t st = EVF_STREAM(stream);
+  const int overwrite = (flags & 2) ? 1 : 0;
+  const int Pm = overwrite ? 1 : P, Pk = Pm;
+  const int HW = H * W;
+  const int comps = overwrite ? 4 : 5;
+  float2* gev = (float2*)ws;
+  unsigned* gmax = (unsigned*)(ws + (size_t)S * B * M * 2);
+  int rc = evf_hip(evf_memset_async(gmax, 0, sizeof(unsigned) * (size_t)S * Pm * B, st));
+  if (rc) return rc;
+  const int gx = evf_cdiv(HW, 256);
+  hipLaunchKernelGGL(k_cm_bwd_pre, dim3(gx * S * Pm * B + gx * S * B * 2), dim3(256), 0, st, flow, mask, S, Pm, Pk, B, H, W, flags & 1,
+                     overwrite ? 0 : 1, grad_out, regul_weight / (float)comps / (float)Pm / (float)S, dflow, images, stats, (float)P,
+                     (flags & 4) ? 1 : 0, gimages);
+  hipLaunchKernelGGL(k_cm_event_grad, dim3(8 * evf_cdiv((long)B * M, 256 * 8), S), dim3(256), 0, st, flow, (const float4*)ev,
+                     (const float2*)pol, ev_pass, S, Pm, P, B, M, H, W, flow_scaling, gimages, gev, gmax);
+  const int rows = cm_det_bwd_rows(S, Pm, B, H, W);
+  const size_t bytes = sizeof(unsigned long long) * 2 * rows * W;
+  static std::once_flag once;
+  std::call_once(once, []() {
+    (void)hipFuncSetAttribute((const void*)k_cm_event_sum_det, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+  });
+  int L = 0;
+  while ((1L << L) < (long)M) ++L;  // ceil(log2 M)
+  hipLaunchKernelGGL(k_cm_event_sum_det, dim3(S * Pm * B, evf_cdiv(H, rows)), dim3(CMD_THREADS), bytes, st, (const float4*)ev, ev_pass,
+                     (const float2*)gev, (const unsigned*)gmax, S, Pm, B, M, H, W, rows, L, dflow);
   return evf_status();
 }
 

@@ -10,6 +10,10 @@ Differences in mechanism, not in results:
     (`evf_cm_loss_fwd`), 3 backward (`evf_cm_loss_bwd`) for all scales.
   * the caller's `event_list` is never mutated (reference quirk q1,
     loss/flow.py:90): the pass offset is added in-register.
+  * `set_deterministic(True)` (or EVF_DETERMINISTIC=1 in the environment) routes
+    `EventWarping` through `evf_cm_loss_fwd_det` / `evf_cm_loss_bwd_det`: exact,
+    order-independent sums instead of float atomics -- bit-identical from run to run.
+    `EVF_CM_BWD_LDS`, `evf_cm_merge` and `CM_LDS_MIN_EVENTS` have no effect in that mode.
 """
 
 import os
@@ -17,6 +21,7 @@ import os
 import torch
 
 from .. import _lib
+from .._lib import deterministic, set_deterministic  # noqa: F401  (re-exported: the switch of the deterministic loss)
 from ..utils.iwe import iwe_splat
 
 
@@ -130,6 +135,31 @@ def _pass_index(lengths, device):
 CM_LDS_MIN_EVENTS = int(os.environ.get("EVF_CM_LDS_MIN_EVENTS", 32768))
 
 
+CM_DET_MIN_LOG2 = 32  # deterministic mode: fewer fraction bits than this are refused (csrc/evf_events.hip)
+
+
+def cm_det_scale_log2(M, P):
+    """k of the deterministic forward: the largest integer with M * max(P, 1) * 2^k < 2^62 (shape alone, never data)."""
+    return 61 - ((int(M) * max(int(P), 1)).bit_length() - 1)
+
+
+def cm_det_grad_exp(max_bits, M):
+    """e of the deterministic backward from the bit pattern of a map's largest |g| and the events per sample:
+    |g| < 2^(max(E,1) - 126) and at most M <= 2^L terms per pixel, so |sum * 2^e| <= 2^61 with e = 187 - L - max(E,1)."""
+    E = (int(max_bits) >> 23) & 0xFF
+    L = max(int(M) - 1, 0).bit_length()  # ceil(log2 M)
+    return 187 - L - max(E, 1)
+
+
+def _det_refusal(M, P, H, W):
+    """Why the deterministic entry points do not serve this shape (None: they do)."""
+    if W > 2048:
+        return f"image rows of {W} pixels: a stripe row of 64-bit slots fits the LDS up to W = 2048"
+    if cm_det_scale_log2(M, P) < CM_DET_MIN_LOG2:
+        return f"M * P = {M * max(P, 1)} events x passes >= 2^30 leaves fewer than {CM_DET_MIN_LOG2} fraction bits for the exact sums"
+    return None
+
+
 class _CMLoss(torch.autograd.Function):
     """EventWarping.forward (loss/flow.py:176-301) as one fused op.
     Inputs: the flow maps, flat over (scale, pass); output: 0-d loss."""
@@ -150,6 +180,22 @@ class _CMLoss(torch.autograd.Function):
         nblk = _lib.load().evf_cm_smooth_blocks(B, Pm, H, W)
         part = torch.empty((S, nblk), dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
+        ctx.det = _lib.deterministic()  # (the mode in force NOW also runs the backward: a toggle in between cannot mix paths)
+        if ctx.det:
+            nws = _lib.load().evf_cm_loss_ws_det(S, B, M, H, W)
+            why = _det_refusal(M, P, H, W)
+            if nws <= 0 or why:  # never a silent fall-back to the atomics
+                raise _lib.EvflowError(f"deterministic contrast loss not supported: {why or 'bad shape'} "
+                                       "(set_deterministic(False) / EVF_DETERMINISTIC=0 selects the float-atomic path)")
+            ws = torch.empty(nws, dtype=torch.float32, device=dev)
+            _lib.call(
+                "evf_cm_loss_fwd_det", _lib.ptr(fl), _lib.ptr(ev), _lib.ptr(pol), _lib.ptr(ev_pass), _lib.ptr(mask), S, P, B, M,
+                H, W, float(meta["flow_scaling"]), float(meta["weight"]), meta["flags"], _lib.ptr(images), _lib.ptr(stats),
+                _lib.ptr(part), _lib.ptr(loss), _lib.ptr(ws), nws,
+            )
+            ctx.meta = meta
+            ctx.save_for_backward(fl, images, stats)
+            return loss.view(())
         # enough event-scale pairs to amortise the pre-warp pass: LDS-striped accumulation instead of global atomics
         nws = _lib.load().evf_cm_loss_ws(S, B, M, H, W) if S * B * M >= CM_LDS_MIN_EVENTS else 0
         ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws > 0 else None
@@ -173,6 +219,18 @@ class _CMLoss(torch.autograd.Function):
         g = g.to(torch.float32).reshape(1).contiguous()
         gim = torch.empty_like(images)
         dflow = torch.empty_like(fl)
+        if ctx.det:
+            nws = _lib.load().evf_cm_loss_bwd_ws_det(S, P, B, M, H, W, meta["flags"])
+            if nws <= 0:
+                raise _lib.EvflowError(f"deterministic contrast loss not supported: {_det_refusal(M, P, H, W) or 'bad shape'}")
+            ws = torch.empty(nws, dtype=torch.float32, device=fl.device)
+            _lib.call(
+                "evf_cm_loss_bwd_det", _lib.ptr(fl), _lib.ptr(ev), _lib.ptr(pol), _lib.ptr(ev_pass), _lib.ptr(mask), S, P, B, M,
+                H, W, float(meta["flow_scaling"]), float(meta["weight"]), meta["flags"], _lib.ptr(images), _lib.ptr(stats),
+                _lib.ptr(g), _lib.ptr(gim), _lib.ptr(dflow), _lib.ptr(ws), nws,
+            )
+            d = dflow.view(S * Pm, B, 2, H, W)
+            return (None,) + tuple(d[i] for i in range(S * Pm))
         _lib.call(
             "evf_cm_loss_bwd", _lib.ptr(fl), _lib.ptr(ev), _lib.ptr(pol), _lib.ptr(ev_pass), _lib.ptr(mask), S, P, B, M, H,
             W, float(meta["flow_scaling"]), float(meta["weight"]), meta["flags"], _lib.ptr(images), _lib.ptr(stats),

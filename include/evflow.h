@@ -136,6 +136,40 @@ int evf_cm_loss_bwd(const float* flow, const float* ev, const float* pol, const 
                     const float* images, const float* stats, const float* grad_out,
                     float* gimages, float* dflow, void* stream);
 
+/* The DETERMINISTIC form of the two calls above: the same loss and gradient, with every sum that the calls above make with float
+ * atomics (the four images of each direction, the image statistics, dL/dflow of the events) made order-independent, so that the
+ * results are a function of the SET of events and bit-identical from run to run, eager or replayed from a hipGraph.  There is no
+ * process-wide switch in the library: a caller chooses this form by calling these entry points (Python: _lib.set_deterministic,
+ * environment EVF_DETERMINISTIC=1).  evf_cm_merge, evf_cm_bwd_lds and the caller's event-count threshold have no effect here.
+ *  - forward: always [pre-warp | smoothness partials | slots cleared] + [striped splat].  A stripe's planes are signed 64-bit
+ *    integers in LDS; every term wt*pol, wt*tau*pol is scaled by 2^k (exact), rounded once to nearest and added with the 64-bit
+ *    LDS integer atomic; one conversion (float)sum * 2^-k at the write-out into the SAME `images` layout.  k is the largest
+ *    integer with M * max(P,1) * 2^k < 2^62 -- a function of the shape alone (2^44 at M = 15000, P = 10; 2^46 at M = 50000,
+ *    P = 1).  The bound ASSUMES polarity weights in [-1, 1] (the reference's masks are 0 / 1) and event times in [0, 1] within
+ *    their pass; beyond it a pixel's integer may wrap.  Image statistics: one slot per (scale, sample, direction, stripe) with a
+ *    single writer, summed in stripe order by the last block.
+ *  - backward: [smoothness gradient | image gradients] + [per-event gradients stored, the maximum magnitude per dL/dflow map
+ *    by an integer atomic max of the bit patterns] + [stripe-owning blocks sum the stored gradients as 64-bit fixed point with
+ *    an exponent taken from that maximum and ceil(log2 M), convert once, add to the smoothness gradient].  A map whose maximum
+ *    is not finite is summed in floats: the affected pixels come out non-finite, their bits are not specified.
+ * evf_cm_loss_ws_det / evf_cm_loss_bwd_ws_det: floats of scratch the call needs; 0 where it is not supported.
+ * ws is mandatory, ws_floats its size in floats.  Errors, all before any launch: EVF_EINVAL for a null argument or
+ * ws_floats below the query's answer; EVF_ENOTSUP for W > 2048 (a stripe row of 64-bit slots) or k < 32, i.e. M * P >= 2^30.
+ * Like every entry point: nothing is allocated, nothing synchronises, no memset nodes (capturable into a hipGraph).
+ * NOT covered by these calls (they are not part of the loss): see DESIGN.md, "Deterministic contrast loss". */
+int64_t evf_cm_loss_ws_det(int S, int B, int M, int H, int W);
+int evf_cm_loss_fwd_det(const float* flow, const float* ev, const float* pol, const int32_t* ev_pass,
+                        const float* mask, int S, int P, int B, int M, int H, int W,
+                        float flow_scaling, float regul_weight, int flags,
+                        float* images, float* stats, float* smooth_part, float* loss, float* ws, int64_t ws_floats,
+                        void* stream);
+int64_t evf_cm_loss_bwd_ws_det(int S, int P, int B, int M, int H, int W, int flags);
+int evf_cm_loss_bwd_det(const float* flow, const float* ev, const float* pol, const int32_t* ev_pass,
+                        const float* mask, int S, int P, int B, int M, int H, int W,
+                        float flow_scaling, float regul_weight, int flags,
+                        const float* images, const float* stats, const float* grad_out,
+                        float* gimages, float* dflow, float* ws, int64_t ws_floats, void* stream);
+
 /* Per-sample reductions used by FWL / RSAT (loss/flow.py:481-579):
  *   evf_image_variance: unbiased variance over H*W of img [B,1,H,W] -> [B]
  *   evf_avg_ts_ratio  : images [B,4,H,W] (I_pos,I_neg,TS_pos,TS_neg) ->
