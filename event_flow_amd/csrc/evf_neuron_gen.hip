@@ -229,8 +229,12 @@ extern "C" int evf_neuron_fwd(int kind, const float* cur, const float* v_prev, c
 // g_P [npix] = d loss / d pooled activity (PLIF/XLIF), g_z_prev only for ALIF (threshold trace reads z).
 // GST: a state gradient arrives from the next pass (g_v_out / g_z_out2 / g_aux_out); PREV: there is a previous state.
 // Absent groups are compile-time zeros: no dummy loads (each costs a texture-addresser slot), no wasted stores.
+// NP2: Q below 64 and NOT a power of two (C = 12, 20, 24, 40, 48 ...): the Q threads of a pixel are no aligned lane group of a
+// wave (a block holds (256 / Q) * Q threads, waves straddle pixels), so neither shuffle reduction applies -- g_P goes through the
+// global atomics of the Q > 64 arm (zeroed by the host wrapper) and every thread adds its channel sums into LDS itself.  A
+// variant of its own: the other instantiations compile exactly as before.
 #define NG_REP 32
-template <int KIND, bool GST, bool PREV>
+template <int KIND, bool GST, bool PREV, bool NP2>
 __global__ void k_neuron_bwd(const float4* __restrict__ g_v_out, const float4* __restrict__ g_z_out,
                              const float4* __restrict__ g_z_out2, const float4* __restrict__ g_aux_out, const float4* __restrict__ v_out,
                              const float4* __restrict__ aux_out, const float4* __restrict__ v_prev,
@@ -261,7 +265,7 @@ __global__ void k_neuron_bwd(const float4* __restrict__ g_v_out, const float4* _
     }
   }
   float s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0}, s3[4] = {0, 0, 0, 0};
-  const int tpp = Q < 64 ? Q : 64;  // threads of one pixel inside a wave (Q is then a power of two <= 64) -- see host check
+  const int tpp = Q < 64 ? Q : 64;  // threads of one pixel inside a wave (Q is then a power of two <= 64, or NP2) -- see host wrapper
   for (long base = 0; base < total; base += stride) {  // uniform trip count: the pixel reduction shuffles
     const long e = base + gtid;
     const bool ok = e < total;
@@ -336,7 +340,7 @@ __global__ void k_neuron_bwd(const float4* __restrict__ g_v_out, const float4* _
       }
     }
     if (KIND == EVF_PLIF || KIND == EVF_XLIF) {
-      if (Q <= 64) {
+      if (!NP2 && Q <= 64) {
         // the Q threads of a pixel are consecutive lanes of one wave
         for (int o = 1; o < tpp; o <<= 1) gPp += __shfl_xor(gPp, o, 64);
         if (ok && cq == 0) g_P[pix] = gPp;
@@ -347,7 +351,7 @@ __global__ void k_neuron_bwd(const float4* __restrict__ g_v_out, const float4* _
   }
   // lanes l, l + Q, l + 2Q ... of a wave own the same channels (Q a power of two below 64): meet in registers first, so
   // that one lane per channel quad and wave issues the LDS float atomics (slow on gfx950)
-  if (Q < 64) {
+  if (!NP2 && Q < 64) {
     for (int o = Q; o < 64; o <<= 1) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -379,7 +383,7 @@ __global__ void k_neuron_bwd(const float4* __restrict__ g_v_out, const float4* _
       }
       __syncthreads();
     }
-  } else if ((int)(threadIdx.x & 63) < Q) {
+  } else if (NP2 || (int)(threadIdx.x & 63) < Q) {  // (NP2: no meeting above, every thread adds)
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int c = 4 * cq + k;
@@ -456,12 +460,12 @@ extern "C" int evf_neuron_bwd(int kind, const float* g_v_out, const float* g_z_o
   if (!v_out || !p0 || !p1 || !g_cur || npix <= 0 || C <= 0 || (C & 3) || C > 1024 || kind < 0 || kind > 3)
     return EVF_EINVAL;
   const int Q = C >> 2;
-  if (Q < 64 && (Q & (Q - 1))) return EVF_EINVAL;  // the in-wave pixel reduction needs a power of two
+  const bool np2 = Q < 64 && (Q & (Q - 1));  // the in-wave reductions need a power of two: the NP2 variants do without them
   if (kind != EVF_LIF && (!p2 || !p3 || !aux_out || (g_v_prev && !g_aux_prev))) return EVF_EINVAL;
   if ((kind == EVF_PLIF || kind == EVF_XLIF) && (!P || !g_P)) return EVF_EINVAL;
   if (kind == EVF_ALIF && g_v_prev && !g_z_prev) return EVF_EINVAL;
   hipStream_t st = EVF_STREAM(stream);
-  if ((kind == EVF_PLIF || kind == EVF_XLIF) && Q > 64) {
+  if ((kind == EVF_PLIF || kind == EVF_XLIF) && (Q > 64 || np2)) {
     const int rc = evf_hip(evf_memset_async(g_P, 0, sizeof(float) * (size_t)npix, st));
     if (rc) return rc;
   }
@@ -477,17 +481,22 @@ extern "C" int evf_neuron_bwd(int kind, const float* g_v_out, const float* g_z_o
   if (nblk <= 256) ws = nullptr;  // (replicas from 32 blocks on: LIF-EV-FlowNet step 6.56 against 6.53 ms)
   const size_t smem = sizeof(float) * 4 * (size_t)C;
   const bool gst = g_v_out || g_z_out2 || g_aux_out, prev = v_prev || z_prev || aux_prev;
-#define NG_BWD_(K, G_, P_)                                                                                                 \
-  hipLaunchKernelGGL((k_neuron_bwd<K, G_, P_>), dim3(nblk), dim3(bs), smem, st, (const float4*)g_v_out, (const float4*)g_z_out, \
+#define NG_BWD_(K, G_, P_, N_)                                                                                             \
+  hipLaunchKernelGGL((k_neuron_bwd<K, G_, P_, N_>), dim3(nblk), dim3(bs), smem, st, (const float4*)g_v_out, (const float4*)g_z_out, \
                      (const float4*)g_z_out2, (const float4*)g_aux_out, (const float4*)v_out, (const float4*)aux_out, (const float4*)v_prev,        \
                      (const float4*)z_prev, (const float4*)aux_prev, P, prm, (long)npix, C, hard_reset, surrogate,         \
                      act_width, (float4*)g_cur, (float4*)g_v_prev, (float4*)g_z_prev, (float4*)g_aux_prev, g_P, ws)
-#define NG_BWD(K)                                   \
-  do {                                              \
-    if (gst && prev) NG_BWD_(K, true, true);        \
-    else if (gst) NG_BWD_(K, true, false);          \
-    else if (prev) NG_BWD_(K, false, true);         \
-    else NG_BWD_(K, false, false);                  \
+#define NG_BWD__(K, N_)                               \
+  do {                                                \
+    if (gst && prev) NG_BWD_(K, true, true, N_);      \
+    else if (gst) NG_BWD_(K, true, false, N_);        \
+    else if (prev) NG_BWD_(K, false, true, N_);       \
+    else NG_BWD_(K, false, false, N_);                \
+  } while (0)
+#define NG_BWD(K)               \
+  do {                          \
+    if (np2) NG_BWD__(K, true); \
+    else NG_BWD__(K, false);    \
   } while (0)
   switch (kind) {
     case EVF_LIF: NG_BWD(EVF_LIF); break;
@@ -496,6 +505,7 @@ extern "C" int evf_neuron_bwd(int kind, const float* g_v_out, const float* g_z_o
     default: NG_BWD(EVF_XLIF); break;
   }
 #undef NG_BWD
+#undef NG_BWD__
 #undef NG_BWD_
   return evf_status();
 }

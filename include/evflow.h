@@ -763,7 +763,11 @@ int evf_neuron_fwd(int kind, const float* cur, const float* v_prev, const float*
  * ws: optional scratch of EVF_NEURON_BWD_WS floats, ZERO on entry and left zero on exit: the blocks' parameter-gradient
  * sums meet in 32 replicas there instead of 1024 blocks adding atomically into the same 2..4 x C words (null: they do); the
  * block that finishes last sums the replicas into the outputs (arrival ticket in the word behind the replicas).  Launches of
- * <= 256 blocks (at least ~8 float4 per thread) add straight into the outputs and leave the scratch alone. */
+ * <= 256 blocks (at least ~8 float4 per thread) add straight into the outputs and leave the scratch alone.
+ * C: every multiple of 4 up to 1024, as for evf_neuron_fwd.  C / 4 a power of two below 64, or >= 64: the sums over a pixel's
+ * channels (g_P) and over a channel's pixels meet in registers across lanes first; any other C / 4 (C = 12, 20, 24, 40, 48 ...) runs
+ * kernel variants of its own without those meetings (g_P by global atomics, every thread adds into the block's LDS sums):
+ * same results up to summation order, speed not measured. */
 #define EVF_NEURON_BWD_WS (32 * 4096 + 64)
 int evf_neuron_bwd(int kind, const float* g_v_out, const float* g_z_out, const float* g_z_out2,
                    const float* g_aux_out, const float* v_out, const float* aux_out, const float* v_prev,

@@ -558,6 +558,51 @@ def test_cell_first_step_without_state_and_residual():
     assert tuple(st.shape) == (2, 1, 8, 6, 9)
 
 
+@pytest.mark.parametrize("C", (24, 48))
+@pytest.mark.parametrize("kind,recurrent", [("lif", True), ("plif", False), ("alif", True), ("xlif", False)])
+def test_cells_with_a_hidden_width_that_is_no_power_of_two(kind, recurrent, C):
+    """Hidden widths 24 and 48 (C / 4 = 6 and 12 channel quads): one step forward and backward against oracle.snn.cell_step, with
+    the tolerances of the golden cells above.  evf_neuron_bwd used to refuse these widths, so the backward raised."""
+    torch.manual_seed(100 * C + len(kind))
+    kw = {"learn_thresh": True} if kind in ("alif", "xlif") else {}
+    cell = CELL_CLS[(kind, recurrent)](4, C, 3, **kw).to(DEV)
+    gen = torch.Generator().manual_seed(C)
+    x_cpu = torch.randn(2, 4, 9, 11, generator=gen)
+    ns = 2 if kind == "lif" else 3
+    st_cpu = torch.randn(ns, 2, C, 9, 11, generator=gen)
+    st_cpu[1] = (torch.rand(2, C, 9, 11, generator=gen) < 0.3).float()
+    if ns == 3:
+        st_cpu[2] = torch.rand(2, C, 9, 11, generator=gen)
+    g_out, g_new = torch.randn(2, C, 9, 11, generator=gen), torch.randn(ns, 2, C, 9, 11, generator=gen)
+    x, st = x_cpu.to(DEV).requires_grad_(True), st_cpu.to(DEV).requires_grad_(True)
+    out, new = cell(x, st)
+    params = dict(cell.named_parameters())
+    grads = torch.autograd.grad([out, new], [x, st] + list(params.values()), [g_out.to(DEV), g_new.to(DEV)], allow_unused=True)
+    # the oracle on the same numbers
+    p = {"c." + k: v.detach().cpu().clone() for k, v in cell.state_dict().items()}
+    for k in params:
+        p["c." + k].requires_grad_(True)
+    xr, sr = x_cpu.clone().requires_grad_(True), st_cpu.clone().requires_grad_(True)
+    o_ref, new_ref = osnn.cell_step(kind, p, "c.", xr, tuple(sr.unbind(0)), recurrent=recurrent, act=cell.activation,
+                                    hard_reset=cell.hard_reset)
+    new_ref = torch.stack(new_ref)
+    ref = torch.autograd.grad([o_ref, new_ref], [xr, sr] + [p["c." + k] for k in params], [g_out, g_new], allow_unused=True)
+    o_ref, new_ref = o_ref.detach().numpy(), new_ref.detach().numpy()
+    th = np.maximum(N(cell.thresh if kind in ("lif", "plif") else cell.t0), 0.01)[None]
+    if kind in ("alif", "xlif"):
+        th = th + np.maximum(N(cell.t1), 0.0)[None] * new_ref[2]
+    safe = np.abs(new_ref[0] - th) > 1e-5
+    assert safe.mean() > 0.999 and np.array_equal(N(out)[safe], o_ref[safe])
+    assert np.array_equal(N(new)[1][safe], new_ref[1][safe])
+    for i in range(0, ns, 2):  # (potential and trace)
+        np.testing.assert_allclose(N(new)[i], new_ref[i], rtol=1e-5, atol=2e-6)
+    close(N(grads[0]), ref[0].numpy(), 2e-5, f"{kind} {C} gx")
+    close(N(grads[1]), ref[1].numpy(), 2e-5, f"{kind} {C} gstate")
+    for (pn, _), gr, rr in zip(params.items(), grads[2:], ref[2:]):
+        rr = rr.numpy() if rr is not None else np.zeros(tuple(params[pn].shape), np.float32)
+        close(N(gr) if gr is not None else np.zeros_like(rr), rr, 1e-4, f"{kind} {C} {pn}")
+
+
 # ------------------------------------------------------------------ ANN FireNet (G8, BASELINE config 1)
 def _ann_cfg():
     return {"num_bins": 2, "base_num_channels": 32, "kernel_size": 3, "encoding": "voxel", "norm_input": False,
