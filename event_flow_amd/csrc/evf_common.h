@@ -18,6 +18,13 @@ static inline int evf_hip(hipError_t e) { return e == hipSuccess ? EVF_OK : -(10
 
 static inline int evf_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Raise kernel KERNEL's dynamic-LDS limit to `bytes`, once per kernel and process: call it in the launcher, before the launch.
+template <auto KERNEL>
+static inline void evf_dynamic_lds_once(size_t bytes) {
+  static const hipError_t once = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  (void)once;
+}
+
 // hipMemsetAsync as a KERNEL.  Inside a captured step a hipMemsetAsync is a memset node, which the runtime executes outside the
 // pre-built AQL packets of the kernel nodes around it; on ROCm 7.2 replays of such graphs returned corrupted results after a
 // hipDeviceSynchronize (train.GraphedWindowStep: loss inf on the first replay behind the synchronize, fine with

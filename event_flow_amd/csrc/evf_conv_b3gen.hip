@@ -575,6 +575,26 @@ extern "C" int evf_conv_split_select(int n) {  // n > 0: force n K splits wherev
   return EVF_OK;
 }
 
+// The ending of every split launch (rc = its status): ws holds ks slabs [M][N] of partial sums.  The caller takes them as they are
+// (*parts = ks), or k_b3_reduce adds them in index order into `out` (bias, accumulate).
+static int b3_finish_split(int rc, int ks, const float* ws, long M, const ConvGeo& g, const float* bias, float* out, int accumulate,
+                           hipStream_t st, int* parts) {
+  if (rc != EVF_OK) return rc;
+  if (parts) {
+    *parts = ks;
+    return EVF_OK;
+  }
+  hipLaunchKernelGGL(k_b3_reduce, dim3(evf_cdiv(M * (g.N >> 2), 256)), dim3(256), 0, st, ws, ks, M, g.N, bias, out, g.ldo, accumulate);
+  return evf_status();
+}
+
+// The staged 3x3 stride-1 kernels that share a signature (evf_conv_b3_family.h), in the order they are offered a product
+struct B3Member {
+  int (*plan)(const float*, int, int, int, int, int, int, bool, int, int);
+  int (*launch)(const float*, int, const void*, const float*, float*, int, int, int, int, int, int, int, int, int, hipStream_t);
+  bool force;  // tests: take the product wherever the operands allow
+};
+
 // ws: caller's scratch of ws_floats floats (may be null): split-K slabs of the layers whose output tiles alone cannot
 // fill the chip (low-resolution, many-channel layers at small batch)
 // parts (may be null): the caller takes the K split's partial sums itself -- when the plan splits, ws [nparts][M][N] is left
@@ -595,71 +615,27 @@ static int b3_launch(const float* src, const void* wp, const float* bias, float*
     const int ks = evf_conv3_b3x_plan(src, g.B, g.OH, g.OW, g.K, g.N, g.lds, exact_from, cap);
     if (ks == 1 && !bias && !accumulate)  // raw sums = the result
       return evf_conv3_b3x_launch(src, g.lds, wp, out, g.ldo, g.B, g.OH, g.OW, g.K, g.N, exact_from, cap, st);
-    if (ks >= 1 && cap >= ks) {
-      const int rc = evf_conv3_b3x_launch(src, g.lds, wp, ws, g.N, g.B, g.OH, g.OW, g.K, g.N, exact_from, cap, st);
-      if (rc != EVF_OK) return rc;
-      if (parts) {
-        *parts = ks;
-        return EVF_OK;
-      }
-      hipLaunchKernelGGL(k_b3_reduce, dim3(evf_cdiv(M * (g.N >> 2), 256)), dim3(256), 0, st, ws, ks, M, g.N, bias, out, g.ldo,
-                         accumulate);
-      return evf_status();
-    }
+    if (ks >= 1 && cap >= ks)
+      return b3_finish_split(evf_conv3_b3x_launch(src, g.lds, wp, ws, g.N, g.B, g.OH, g.OW, g.K, g.N, exact_from, cap, st), ks, ws, M, g,
+                             bias, out, accumulate, st, parts);
   }
-  // low-resolution many-channel 3x3 stride-1 layers (images of at most 16 x 16): one block per image x 64 output channels x K
-  // split (evf_conv_b3img.hip); EVF_CONV_IMG=0 disables
   if (g.ksz == 3 && g.stride == 1 && b3_tile_mode() != 0) {
-    const int ks = evf_conv3_b3i_plan(src, g.B, g.OH, g.OW, g.K, g.N, g.lds, b3_tile_mode() == 2, (int)min(cap, 8L), b3_split_force());
-    if (ks == 1)
-      return evf_conv3_b3i_launch(src, g.lds, wp, bias, out, g.ldo, g.B, g.OH, g.OW, g.K, g.N, g.mode, accumulate, 1, st);
-    if (ks > 1) {
-      const int rc = evf_conv3_b3i_launch(src, g.lds, wp, nullptr, ws, g.N, g.B, g.OH, g.OW, g.K, g.N, g.mode, 0, ks, st);
-      if (rc != EVF_OK) return rc;
-      if (parts) {
-        *parts = ks;
-        return EVF_OK;
-      }
-      hipLaunchKernelGGL(k_b3_reduce, dim3(evf_cdiv(M * (g.N >> 2), 256)), dim3(256), 0, st, ws, ks, M, g.N, bias, out, g.ldo,
-                         accumulate);
-      return evf_status();
-    }
-  }
-  // 3x3 stride-1 layers with three or more 32-channel output tiles per input tile (the decoders' input gradients): the halo staged
-  // once per channel group, the output channels streaming past it (evf_conv_b3n.hip); EVF_CONV_NSTREAM=0 disables
-  if (g.ksz == 3 && g.stride == 1 && b3_tile_mode() != 0) {
-    const int ks = evf_conv3_b3n_plan(src, g.B, g.OH, g.OW, g.K, g.N, g.lds, b3_tile_mode() == 2 && b3_nstream_forced(), (int)min(cap, 8L),
-                                      b3_split_force());
-    if (ks == 1)
-      return evf_conv3_b3n_launch(src, g.lds, wp, bias, out, g.ldo, g.B, g.OH, g.OW, g.K, g.N, g.mode, accumulate, 1, st);
-    if (ks > 1) {
-      const int rc = evf_conv3_b3n_launch(src, g.lds, wp, nullptr, ws, g.N, g.B, g.OH, g.OW, g.K, g.N, g.mode, 0, ks, st);
-      if (rc != EVF_OK) return rc;
-      if (parts) {
-        *parts = ks;
-        return EVF_OK;
-      }
-      hipLaunchKernelGGL(k_b3_reduce, dim3(evf_cdiv(M * (g.N >> 2), 256)), dim3(256), 0, st, ws, ks, M, g.N, bias, out, g.ldo,
-                         accumulate);
-      return evf_status();
-    }
-  }
-  // wide high-resolution 3x3 stride-1 layers: the spatially tiled kernel (evf_conv_b3tile.hip); EVF_CONV_TILE=0 disables
-  if (g.ksz == 3 && g.stride == 1 && b3_tile_mode() != 0) {
-    const int ks = evf_conv3_b3t_plan(src, g.B, g.OH, g.OW, g.K, g.N, g.lds, b3_tile_mode() == 2, (int)min(cap, 8L),
-                                      b3_split_force());
-    if (ks == 1)
-      return evf_conv3_b3t_launch(src, g.lds, wp, bias, out, g.ldo, g.B, g.OH, g.OW, g.K, g.N, g.mode, accumulate, 1, st);
-    if (ks > 1) {
-      const int rc = evf_conv3_b3t_launch(src, g.lds, wp, nullptr, ws, g.N, g.B, g.OH, g.OW, g.K, g.N, g.mode, 0, ks, st);
-      if (rc != EVF_OK) return rc;
-      if (parts) {
-        *parts = ks;
-        return EVF_OK;
-      }
-      hipLaunchKernelGGL(k_b3_reduce, dim3(evf_cdiv(M * (g.N >> 2), 256)), dim3(256), 0, st, ws, ks, M, g.N, bias, out, g.ldo,
-                         accumulate);
-      return evf_status();
+    const bool forced = b3_tile_mode() == 2;
+    const B3Member members[3] = {
+        // low-resolution many-channel layers (images of at most 16 x 16): one block per image x 64 output channels x K split
+        // (evf_conv_b3img.hip); EVF_CONV_IMG=0 disables
+        {evf_conv3_b3i_plan, evf_conv3_b3i_launch, forced},
+        // three or more 32-channel output tiles per input tile (the decoders' input gradients): the halo staged once per channel
+        // group, the output channels streaming past it (evf_conv_b3n.hip); EVF_CONV_NSTREAM=0 disables
+        {evf_conv3_b3n_plan, evf_conv3_b3n_launch, forced && b3_nstream_forced()},
+        // wide high-resolution layers: the spatially tiled kernel (evf_conv_b3tile.hip); EVF_CONV_TILE=0 disables
+        {evf_conv3_b3t_plan, evf_conv3_b3t_launch, forced}};
+    for (const B3Member& m : members) {
+      const int ks = m.plan(src, g.B, g.OH, g.OW, g.K, g.N, g.lds, m.force, (int)min(cap, 8L), b3_split_force());
+      if (ks == 1) return m.launch(src, g.lds, wp, bias, out, g.ldo, g.B, g.OH, g.OW, g.K, g.N, g.mode, accumulate, 1, st);
+      if (ks > 1)
+        return b3_finish_split(m.launch(src, g.lds, wp, nullptr, ws, g.N, g.B, g.OH, g.OW, g.K, g.N, g.mode, 0, ks, st), ks, ws, M, g, bias,
+                               out, accumulate, st, parts);
     }
   }
   const bool par = g.mode == 1 && g.stride == 2 && g.ksz == 3;
@@ -682,14 +658,7 @@ static int b3_launch(const float* src, const void* wp, const float* bias, float*
     g2.ldo = g.N;
     const int rc = two ? b3_launch_vec<2, false>(src, wp, nullptr, ws, g2, 0, st, nsplit)
                        : b3_launch_vec<1, false>(src, wp, nullptr, ws, g2, 0, st, nsplit);
-    if (rc != EVF_OK) return rc;
-    if (parts) {
-      *parts = nsplit;
-      return EVF_OK;
-    }
-    hipLaunchKernelGGL(k_b3_reduce, dim3(evf_cdiv(M * (g.N >> 2), 256)), dim3(256), 0, st, ws, nsplit, M, g.N, bias, out,
-                       g.ldo, accumulate);
-    return evf_status();
+    return b3_finish_split(rc, nsplit, ws, M, g, bias, out, accumulate, st, parts);
   }
   if (two) return b3_launch_vec<2, false>(src, wp, bias, out, g, accumulate, st);
   return b3_launch_vec<1, false>(src, wp, bias, out, g, accumulate, st);

@@ -13,20 +13,16 @@
 //             once per group and reused by the nine taps: a group is 9 x 48 MFMAs per wave between A-tile barriers (the tiled
 //             kernel: 108); the weights of one tap (4 chunks x NT x 3 planes x 1 KiB) double-buffered through registers
 //   head      a decoder's input starts with its two real-valued flow channels (exact_from = 4): channels 0..15 run FIRST as the
-//             exact 3-way split (three planes, the six products above 2^-24), through the same LDS, by the K split 0
+//             exact 3-way split (three planes, the six products above 2^-24), through the same LDS, by the K split 0.  Its
+//             split-and-store, and the order of the three and of the six products, are the family's (evf_conv_b3_family.h);
+//             the staging of the exact plane, the weight index per tap and the raw-sum store are this kernel's own
 //   output    raw partial sums: [split][pixel][N] slabs (added in index order by k_b3_reduce or by the neuron kernel,
 //             evf_lif_fwd_parts), or the output tensor itself when the contraction is not split; weights are the A operand, so a
 //             lane owns a pixel and stores float4s
 //   guard     an input value behind exact_from that is NOT exactly representable in bf16 (the caller's promise broken) turns the
 //             block's output into NaN -- never a silently rounded product.
 // Measured (LIF-EV-FlowNet step, B = 8): the five 512 -> 512 layers at 16 x 16 75 -> 35 us each (GEOM 0).
-#include "evf_common.h"
-#include "evf_split.h"
-
-typedef float s_f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 s_bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t s_u32x4 __attribute__((ext_vector_type(4)));
-typedef float s_f32x4 __attribute__((ext_vector_type(4)));
+#include "evf_conv_b3_family.h"
 
 #define SX_KB 64                        // input channels per group
 #define SX_PITCH (SX_KB * 2 + 16)       // 144 bytes per halo pixel of the exact plane
@@ -77,7 +73,7 @@ __global__ __launch_bounds__(512) void k_conv3_b3x(const float* __restrict__ src
     return (((long)b0 * g.H + min(max(sy, 0), g.H - 1)) * g.W + min(max(sx, 0), g.W - 1)) * g.lds;
   };
 
-  s_f32x16 acc[2][NT];
+  b3_f32x16 acc[2][NT];
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -104,18 +100,10 @@ __global__ __launch_bounds__(512) void k_conv3_b3x(const float* __restrict__ src
       bool in;
       const long off = hsrc(hp, in);
       const int c = 4 * q;
-      const s_f32x4 v = *(const s_f32x4*)(src + off + (c + 4 <= g.K ? c : 0));
-      const s_f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-      const s_f32x4 a = (in && c + 4 <= g.K) ? v : z4;
-      uint32_t h0, m0, l0, h1, m1, l1;
-      evf_split3_pair(a.x, a.y, h0, m0, l0);
-      evf_split3_pair(a.z, a.w, h1, m1, l1);
-      if (tid + 512 * j < HT) {
-        char* d = s_a + hp * SX_APITCH + q * 8;
-        *(uint2*)(d) = make_uint2(h0, h1);
-        *(uint2*)(d + HPL) = make_uint2(m0, m1);
-        *(uint2*)(d + 2 * HPL) = make_uint2(l0, l1);
-      }
+      const b3_f32x4 v = *(const b3_f32x4*)(src + off + (c + 4 <= g.K ? c : 0));
+      const b3_f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+      const b3_f32x4 a = (in && c + 4 <= g.K) ? v : z4;
+      (void)b3_split_store(a, s_a + hp * SX_APITCH + q * 8, HPL, tid + 512 * j < HT);
     }
     // all nine taps' weights of chunk 0: [tap][N tile][term][lane]
     constexpr int HW = 9 * NT * SX_CHUNK;
@@ -127,27 +115,20 @@ __global__ __launch_bounds__(512) void k_conv3_b3x(const float* __restrict__ src
 #pragma unroll 1
     for (int tap = 0; tap < 9; ++tap) {
       const int dy = tap / 3, dx = tap - 3 * dy;
-      s_bf16x8 xh[2], xm[2], xl[2];
+      b3_bf16x8 xh[2], xm[2], xl[2];
 #pragma unroll
       for (int m = 0; m < 2; ++m) {
         const char* ap = s_a + (hpix[m] + dy * HPW + dx) * SX_APITCH + kg * 16;
         const uint4 a0 = *(const uint4*)ap, a1 = *(const uint4*)(ap + HPL), a2 = *(const uint4*)(ap + 2 * HPL);
-        xh[m] = *(const s_bf16x8*)&a0, xm[m] = *(const s_bf16x8*)&a1, xl[m] = *(const s_bf16x8*)&a2;
+        xh[m] = *(const b3_bf16x8*)&a0, xm[m] = *(const b3_bf16x8*)&a1, xl[m] = *(const b3_bf16x8*)&a2;
       }
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         const uint4* wq = s_w + (tap * NT + t) * SX_CHUNK + lane;
         const uint4 q0 = wq[0], q1 = wq[64], q2 = wq[128];
-        const s_bf16x8 wh = *(const s_bf16x8*)&q0, wm = *(const s_bf16x8*)&q1, wl = *(const s_bf16x8*)&q2;
+        const b3_bf16x8 wh = *(const b3_bf16x8*)&q0, wm = *(const b3_bf16x8*)&q1, wl = *(const b3_bf16x8*)&q2;
 #pragma unroll
-        for (int m = 0; m < 2; ++m) {  // smallest terms first
-          acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xm[m], acc[m][t], 0, 0, 0);
-          acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xh[m], acc[m][t], 0, 0, 0);
-          acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xl[m], acc[m][t], 0, 0, 0);
-          acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xh[m], acc[m][t], 0, 0, 0);
-          acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xm[m], acc[m][t], 0, 0, 0);
-          acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xh[m], acc[m][t], 0, 0, 0);
-        }
+        for (int m = 0; m < 2; ++m) b3_mma6(acc[m][t], wh, wm, wl, xh[m], xm[m], xl[m]);
       }
     }
     __syncthreads();  // (the plane region and the weight region are rewritten by the groups below)
@@ -156,7 +137,7 @@ __global__ __launch_bounds__(512) void k_conv3_b3x(const float* __restrict__ src
   // ---- the exact groups of this K split
   const int ngroups = (g.nchunk + 3) >> 2;
   const int g_lo = min(ks * g.gper, ngroups), g_hi = min(g_lo + g.gper, ngroups);
-  s_u32x4 pw[WJ];
+  b3_u32x4 pw[WJ];
   auto wfetch = [&](int grp, int tap) {  // the tap's weights of the group's chunks: [N tile][chunk 4][term][lane]
     const int c16 = g.chunk0 + 4 * grp;
 #pragma unroll
@@ -164,13 +145,13 @@ __global__ __launch_bounds__(512) void k_conv3_b3x(const float* __restrict__ src
       const int idx = min(tid + 512 * j, WSTAGE - 1), t = idx / (4 * SX_CHUNK), r = idx - t * (4 * SX_CHUNK), ch = r / SX_CHUNK,
                 rem = r - ch * SX_CHUNK;
       const int cc = min(c16 + ch, KC - 1);  // (a chunk past the end re-reads the last one: its plane is zero)
-      pw[j] = ((const s_u32x4*)wp)[(long)min(nb * NT + t, ntiles - 1) * wtile + ((long)tap * G * 4 + cc) * SX_CHUNK + rem];
+      pw[j] = ((const b3_u32x4*)wp)[(long)min(nb * NT + t, ntiles - 1) * wtile + ((long)tap * G * 4 + cc) * SX_CHUNK + rem];
     }
   };
   auto wcommit = [&](int stage) {
 #pragma unroll
     for (int j = 0; j < WJ; ++j)
-      if (tid + 512 * j < WSTAGE) ((s_u32x4*)s_w)[stage * WSTAGE + tid + 512 * j] = pw[j];
+      if (tid + 512 * j < WSTAGE) ((b3_u32x4*)s_w)[stage * WSTAGE + tid + 512 * j] = pw[j];
   };
 #pragma unroll 1
   for (int grp = g_lo; grp < g_hi; ++grp) {
@@ -180,7 +161,7 @@ __global__ __launch_bounds__(512) void k_conv3_b3x(const float* __restrict__ src
     constexpr int AU = GEOM == 0 ? 7 : 5;  // AITER = 21 = 3 x 7 / 20 = 4 x 5
 #pragma unroll 1
     for (int j0 = 0; j0 < AITER; j0 += AU) {
-      s_f32x4 v[AU];
+      b3_f32x4 v[AU];
       bool in[AU];
 #pragma unroll
       for (int jj = 0; jj < AU; ++jj) {
@@ -188,13 +169,13 @@ __global__ __launch_bounds__(512) void k_conv3_b3x(const float* __restrict__ src
         const long off = hsrc(hp, in[jj]);
         const int c = k0 + 4 * q;
         in[jj] = in[jj] && c + 4 <= g.K;
-        v[jj] = *(const s_f32x4*)(src + off + (c + 4 <= g.K ? c : 0));
+        v[jj] = *(const b3_f32x4*)(src + off + (c + 4 <= g.K ? c : 0));
       }
 #pragma unroll
       for (int jj = 0; jj < AU; ++jj) {
         const int task = tid + 512 * (j0 + jj), hp = task >> 4, q = task & 15;
-        const s_f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-        const s_f32x4 a = in[jj] ? v[jj] : z4;
+        const b3_f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+        const b3_f32x4 a = in[jj] ? v[jj] : z4;
         const uint32_t h01 = evf_pk_bf16(a.x, a.y), h23 = evf_pk_bf16(a.z, a.w);
         inexact |= (int)(a.x != __uint_as_float(h01 << 16)) | (int)(a.y != __uint_as_float(h01 & 0xFFFF0000u)) |
                    (int)(a.z != __uint_as_float(h23 << 16)) | (int)(a.w != __uint_as_float(h23 & 0xFFFF0000u));
@@ -215,17 +196,13 @@ __global__ __launch_bounds__(512) void k_conv3_b3x(const float* __restrict__ src
       for (int ch = 0; ch < 4; ++ch) {
         if (ch < nch) {
           const uint4 x0q = *(const uint4*)(a0p + ch * 32), x1q = *(const uint4*)(a1p + ch * 32);
-          const s_bf16x8 xa = *(const s_bf16x8*)&x0q, xb = *(const s_bf16x8*)&x1q;
+          const b3_bf16x8 xa = *(const b3_bf16x8*)&x0q, xb = *(const b3_bf16x8*)&x1q;
 #pragma unroll
           for (int t = 0; t < NT; ++t) {
             const uint4 q0 = sw[((t * 4 + ch) * 3 + 0) * 64], q1 = sw[((t * 4 + ch) * 3 + 1) * 64], q2 = sw[((t * 4 + ch) * 3 + 2) * 64];
-            const s_bf16x8 wh = *(const s_bf16x8*)&q0, wm = *(const s_bf16x8*)&q1, wl = *(const s_bf16x8*)&q2;
-            acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xa, acc[0][t], 0, 0, 0);  // smallest terms first
-            acc[1][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xb, acc[1][t], 0, 0, 0);
-            acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xa, acc[0][t], 0, 0, 0);
-            acc[1][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xb, acc[1][t], 0, 0, 0);
-            acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xa, acc[0][t], 0, 0, 0);
-            acc[1][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xb, acc[1][t], 0, 0, 0);
+            const b3_bf16x8 wh = *(const b3_bf16x8*)&q0, wm = *(const b3_bf16x8*)&q1, wl = *(const b3_bf16x8*)&q2;
+            b3_mma3(acc[0][t], wh, wm, wl, xa);
+            b3_mma3(acc[1][t], wh, wm, wl, xb);
           }
         }
       }
@@ -320,11 +297,7 @@ int evf_conv3_b3x_launch(const float* src, int lds, const void* wp, float* dst, 
   const dim3 grid(p.geom == 0 ? B / 2 : B * g.tiles_y * g.tiles_x, evf_cdiv(N, 32 * p.NT), p.ksplit);
 #define SX_GO(G_, T_)                                                                                                       \
   do {                                                                                                                      \
-    static bool once = false;                                                                                               \
-    if (!once) {                                                                                                            \
-      (void)hipFuncSetAttribute((const void*)k_conv3_b3x<G_, T_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);   \
-      once = true;                                                                                                          \
-    }                                                                                                                       \
+    evf_dynamic_lds_once<k_conv3_b3x<G_, T_>>(smem);                                                                        \
     hipLaunchKernelGGL((k_conv3_b3x<G_, T_>), grid, dim3(512), smem, st, src, (const uint4*)wp, dst, g);                    \
   } while (0)
   if (p.geom == 0 && p.NT == 2) SX_GO(0, 2);

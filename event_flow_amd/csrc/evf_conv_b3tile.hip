@@ -1,11 +1,8 @@
 // 3x3 stride-1 convolution (forward and input gradient) of wide, high-resolution layers: spatially tiled, the halo tile of
 // the input staged ONCE per 16-channel group in LDS as bf16 split planes -- read from HBM once, converted once, reused by
 // the nine taps and by every output channel of the block -- against k_conv2d_b3 (evf_conv_b3gen.hip), whose waves re-read
-// and re-convert their pixels per tap and whose LDS pipe carries one weight fragment per MFMA.  Same arithmetic: weights
-// w = hi + mid + lo (three bf16 planes, the packed operand of evf_pack_conv2d_weight_b3), activations as bf16 head +
-// residual planes, v_mfma_f32_32x32x16_bf16 with fp32 accumulation; a block-uniform vote per channel group (are all
-// residuals of the staged tile zero?) picks 3 products (spikes, counts, bilinear blends of spikes) or the 6 terms above
-// 2^-24 of the leading one.  The vote never changes a result.
+// and re-convert their pixels per tap and whose LDS pipe carries one weight fragment per MFMA.  Operands, staging, the
+// products and their order and the split-K range are the family's (evf_conv_b3_family.h).
 //
 //   block      512 threads = 8 waves, output tile 16 rows x 32 columns, 32*NT output channels; wave w owns rows 2w, 2w+1
 //              (two 32-pixel M tiles sharing every weight fragment: 2 + 3 NT LDS fragment reads per 6 NT MFMAs)
@@ -15,24 +12,14 @@
 //              written to LDS after it (two barriers per group)
 //   epilogue   weights are the A operand: the tile comes out transposed, a lane owns one pixel and 4 x 4 consecutive
 //              channels per N tile -> float4 stores (bias, accumulate)
-#include "evf_common.h"
-#include "evf_split.h"
-
-typedef float t_f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 t_bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t t_u32x4 __attribute__((ext_vector_type(4)));
-typedef float t_f32x4 __attribute__((ext_vector_type(4)));
+#include "evf_conv_b3_family.h"
 
 #define T_ROWS 16
 #define T_COLS 32
-#define T_HR (T_ROWS + 2)
-#define T_HC (T_COLS + 2)
-#define T_PIX (T_HR * T_HC)          // 612 halo pixels
-#define T_PSTRIDE 48                 // bytes per halo pixel and plane
-#define T_PLANE (T_PIX * T_PSTRIDE)  // 29376
-#define T_ATASKS (T_PIX * 4)         // float4 loads per group
-#define T_AITER ((T_ATASKS + 511) / 512)
-#define B3_STAGE (4 * 3 * 64)  // uint4 per (N tile, tap, 64-channel group) of the packed weights: [chunk 4][term 3][lane 64]
+typedef B3Halo<T_ROWS, T_COLS, 512> THalo;  // 612 halo pixels, 29376 B per plane
+#define T_HC (THalo::HC)
+#define T_PSTRIDE (THalo::PITCH)
+#define T_PLANE (THalo::PLANE)
 
 struct TileGeo {
   int B, H, W, K, N;  // image (input = output size), contraction channels, output channels
@@ -46,11 +33,6 @@ struct TileGeo {
 // the allocator settled on 128 and spilled 64 bytes (NT = 2); with it the LIF-EV-FlowNet input gradients run 4 % faster.
 #ifndef B3T_WAVES_ATTR
 #define B3T_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(2, 2)))
-#endif
-#ifdef B3T_UNROLL_OX  // (A/B: the three taps of a kernel row unrolled, so that the next tap's fragment reads may issue under this tap's MFMAs)
-#define B3T_OX_LOOP _Pragma("unroll")
-#else
-#define B3T_OX_LOOP _Pragma("unroll 1")
 #endif
 template <int NT>
 __global__ __launch_bounds__(512) B3T_WAVES_ATTR void k_conv3_b3t(const float* __restrict__ src, const uint4* __restrict__ wp,
@@ -74,57 +56,29 @@ __global__ __launch_bounds__(512) B3T_WAVES_ATTR void k_conv3_b3t(const float* _
   const int nt_base = g.nt_off + (int)blockIdx.y * NT;
 
   // ---- staging: global -> registers (before the matrix phase) -> LDS (after it)
-  t_f32x4 pa[T_AITER];
-  t_u32x4 pw[WITER];
+  b3_f32x4 pa[THalo::ITER];
+  b3_u32x4 pw[WITER];
   const float* img = src + (long)b * g.H * g.W * g.lds;
   auto fetch = [&](int kc) {
-#pragma unroll
-    for (int i = 0; i < T_AITER; ++i) {
-      const int task = min(tid + 512 * i, T_ATASKS - 1), px = task >> 2, q = task & 3;
-      const int hy = px / T_HC, hx = px - hy * T_HC;
-      const int sy = min(max(y0 + hy - 1, 0), g.H - 1), sx = min(max(x0 + hx - 1, 0), g.W - 1);
-      const int c = kc * 16 + 4 * q;
-      pa[i] = *(const t_f32x4*)(img + ((long)sy * g.W + sx) * g.lds + (c + 4 <= g.K ? c : 0));
-    }
-    const int gg = kc >> 2, ch = kc & 3;
+    THalo::fetch(pa, img, y0, x0, g, kc, tid);
 #pragma unroll
     for (int i = 0; i < WITER; ++i) {
       const int idx = min(tid + 512 * i, WFRAG - 1), ln = idx & 63, f = idx >> 6;
       const int term = f % 3, f2 = f / 3, tap = f2 % 9, t = f2 / 9;
-      pw[i] = ((const t_u32x4*)wp)[min(nt_base + t, ntiles - 1) * wtile + (((long)tap * G64 + gg) * 4 + ch) * 192 + term * 64 + ln];
+      pw[i] = *(const b3_u32x4*)b3_wfrag(wp + min(nt_base + t, ntiles - 1) * wtile, tap, G64, kc, term, ln);
     }
   };
-  // returns "some residual is not zero" for this thread's elements
   auto commit = [&](int kc) -> int {
-    uint32_t nz = 0u;
-#pragma unroll
-    for (int i = 0; i < T_AITER; ++i) {
-      const int task = tid + 512 * i, px = task >> 2, q = task & 3;
-      const int hy = px / T_HC, hx = px - hy * T_HC;
-      const int sy = y0 + hy - 1, sx = x0 + hx - 1;
-      const bool ok = sy >= 0 && sy < g.H && sx >= 0 && sx < g.W && kc * 16 + 4 * q + 4 <= g.K;
-      const t_f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-      const t_f32x4 v = ok ? pa[i] : zero4;
-      uint32_t h0, m0, l0, h1, m1, l1;
-      evf_split3_pair(v.x, v.y, h0, m0, l0);
-      evf_split3_pair(v.z, v.w, h1, m1, l1);
-      nz |= m0 | m1;  // (mid = bf16(residual): zero iff the residual is zero; -0 cannot arise from x - head(x))
-      if (task < T_ATASKS) {
-        char* p = s_a + px * T_PSTRIDE + q * 8;
-        *(uint2*)(p) = make_uint2(h0, h1);
-        *(uint2*)(p + T_PLANE) = make_uint2(m0, m1);
-        *(uint2*)(p + 2 * T_PLANE) = make_uint2(l0, l1);
-      }
-    }
+    const int nz = THalo::commit(pa, s_a, y0, x0, g, kc, tid);
 #pragma unroll
     for (int i = 0; i < WITER; ++i) {
       const int idx = tid + 512 * i;
-      if (idx < WFRAG) ((t_u32x4*)s_w)[idx] = pw[i];
+      if (idx < WFRAG) ((b3_u32x4*)s_w)[idx] = pw[i];
     }
-    return (nz & 0x7FFF7FFFu) != 0u;
+    return nz;
   };
 
-  t_f32x16 acc[2][NT];
+  b3_f32x16 acc[2][NT];
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -133,13 +87,9 @@ __global__ __launch_bounds__(512) B3T_WAVES_ATTR void k_conv3_b3t(const float* _
       for (int r = 0; r < 16; ++r) acc[m][t][r] = 0.f;
 
   // split-K: blockIdx.z owns the channel groups [kc_lo, kc_hi) and writes its partial sums to its own slab
-  int kc_lo = 0, kc_hi = KC;
-  if (ksplit > 1) {
-    const int per = (KC + ksplit - 1) / ksplit;
-    kc_lo = min((int)blockIdx.z * per, KC - 1), kc_hi = min(kc_lo + per, KC);
-    if ((int)blockIdx.z * per >= KC) kc_hi = kc_lo;  // (an empty split still writes its zeros)
-    out += (long)blockIdx.z * g.B * g.H * g.W * g.ldo;
-  }
+  int kc_lo, kc_hi;
+  b3_split_range(KC, ksplit, (int)blockIdx.z, kc_lo, kc_hi);
+  if (ksplit > 1) out += (long)blockIdx.z * g.B * g.H * g.W * g.ldo;
   fetch(kc_lo);
   int inexact = __syncthreads_or(commit(kc_lo));
 
@@ -151,54 +101,43 @@ __global__ __launch_bounds__(512) B3T_WAVES_ATTR void k_conv3_b3t(const float* _
     if (!inexact) {
 #pragma unroll 1
       for (int oy = 0; oy < 3; ++oy) {
-        B3T_OX_LOOP
+#pragma unroll 1
         for (int ox = 0; ox < 3; ++ox) {
           const int wtap = g.flip ? (2 - oy) * 3 + (2 - ox) : oy * 3 + ox;
           const char* ap = arow + (oy * T_HC + ox) * T_PSTRIDE;
           const uint4* wq = s_w + wtap * 192 + lane;
           const uint4 x0q = *(const uint4*)ap, x1q = *(const uint4*)(ap + T_HC * T_PSTRIDE);
-          const t_bf16x8 xa = *(const t_bf16x8*)&x0q, xb = *(const t_bf16x8*)&x1q;
+          const b3_bf16x8 xa = *(const b3_bf16x8*)&x0q, xb = *(const b3_bf16x8*)&x1q;
 #pragma unroll
           for (int t = 0; t < NT; ++t) {
             const uint4 q0 = wq[t * 27 * 64], q1 = wq[t * 27 * 64 + 64], q2 = wq[t * 27 * 64 + 128];
-            const t_bf16x8 wh = *(const t_bf16x8*)&q0, wm = *(const t_bf16x8*)&q1, wl = *(const t_bf16x8*)&q2;
-            acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xa, acc[0][t], 0, 0, 0);  // smallest terms first
-            acc[1][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xb, acc[1][t], 0, 0, 0);
-            acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xa, acc[0][t], 0, 0, 0);
-            acc[1][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xb, acc[1][t], 0, 0, 0);
-            acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xa, acc[0][t], 0, 0, 0);
-            acc[1][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xb, acc[1][t], 0, 0, 0);
+            const b3_bf16x8 wh = *(const b3_bf16x8*)&q0, wm = *(const b3_bf16x8*)&q1, wl = *(const b3_bf16x8*)&q2;
+            b3_mma3(acc[0][t], wh, wm, wl, xa);
+            b3_mma3(acc[1][t], wh, wm, wl, xb);
           }
         }
       }
     } else {
 #pragma unroll 1
       for (int oy = 0; oy < 3; ++oy) {
-        B3T_OX_LOOP
+#pragma unroll 1
         for (int ox = 0; ox < 3; ++ox) {
           const int wtap = g.flip ? (2 - oy) * 3 + (2 - ox) : oy * 3 + ox;
           const char* ap = arow + (oy * T_HC + ox) * T_PSTRIDE;
           const uint4* wq = s_w + wtap * 192 + lane;
-          t_bf16x8 xh[2], xm[2], xl[2];
+          b3_bf16x8 xh[2], xm[2], xl[2];
 #pragma unroll
           for (int m = 0; m < 2; ++m) {
             const uint4 a0 = *(const uint4*)(ap + m * T_HC * T_PSTRIDE), a1 = *(const uint4*)(ap + m * T_HC * T_PSTRIDE + T_PLANE),
                         a2 = *(const uint4*)(ap + m * T_HC * T_PSTRIDE + 2 * T_PLANE);
-            xh[m] = *(const t_bf16x8*)&a0, xm[m] = *(const t_bf16x8*)&a1, xl[m] = *(const t_bf16x8*)&a2;
+            xh[m] = *(const b3_bf16x8*)&a0, xm[m] = *(const b3_bf16x8*)&a1, xl[m] = *(const b3_bf16x8*)&a2;
           }
 #pragma unroll
           for (int t = 0; t < NT; ++t) {
             const uint4 q0 = wq[t * 27 * 64], q1 = wq[t * 27 * 64 + 64], q2 = wq[t * 27 * 64 + 128];
-            const t_bf16x8 wh = *(const t_bf16x8*)&q0, wm = *(const t_bf16x8*)&q1, wl = *(const t_bf16x8*)&q2;
+            const b3_bf16x8 wh = *(const b3_bf16x8*)&q0, wm = *(const b3_bf16x8*)&q1, wl = *(const b3_bf16x8*)&q2;
 #pragma unroll
-            for (int m = 0; m < 2; ++m) {  // smallest terms first
-              acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xm[m], acc[m][t], 0, 0, 0);
-              acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xh[m], acc[m][t], 0, 0, 0);
-              acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xl[m], acc[m][t], 0, 0, 0);
-              acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xh[m], acc[m][t], 0, 0, 0);
-              acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xm[m], acc[m][t], 0, 0, 0);
-              acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xh[m], acc[m][t], 0, 0, 0);
-            }
+            for (int m = 0; m < 2; ++m) b3_mma6(acc[m][t], wh, wm, wl, xh[m], xm[m], xl[m]);
           }
         }
       }
@@ -207,7 +146,9 @@ __global__ __launch_bounds__(512) B3T_WAVES_ATTR void k_conv3_b3t(const float* _
     if (kc + 1 < kc_hi) inexact = __syncthreads_or(commit(kc + 1));
   }
 
-  // ---- epilogue: lane = pixel (row 2wv + m, column col); channels n0 + 8q + 4kg + e
+  // ---- epilogue: lane = pixel (row 2wv + m, column col); channels n0 + 8q + 4kg + e.  Not b3_store_tile: the old values and the
+  // bias are loaded ahead of the `mok` branch here, and with the shared store the kernel compiles to other resource figures
+  // (NT = 1: 100 scalar registers for 76; NT = 2: 14 spilled registers for 15) that nobody has measured.
   const bool vec = (g.ldo & 3) == 0 && (((uintptr_t)out) & 15) == 0;  // uniform
 #pragma unroll
   for (int m = 0; m < 2; ++m) {
@@ -270,9 +211,7 @@ int evf_conv3_b3t_plan(const float* src, int B, int H, int W, int K, int N, int 
   const long tiles = (long)B * evf_cdiv(H, T_ROWS) * evf_cdiv(W, T_COLS);
   const long blocks = tiles * evf_cdiv(N, N > 32 ? 64 : 32);
   const int KC = evf_cdiv(K, 16);
-  const int smax = max(1, min(max_split, KC / 4));  // at least 4 channel groups per split
-  int ks = blocks >= 256 ? 1 : (int)min((long)smax, evf_cdiv(512L, blocks));  // (less than one block per CU: split)
-  if (force_split > 0) ks = max(1, min(min(force_split, max(max_split, 1)), KC));
+  const int ks = b3_plan_splits(blocks, KC, max_split, force_split, 256, 512);  // (less than one block per CU: split)
   if (force) return ks;
   // enough blocks for the 256 CUs, and tiles that are mostly inside the image
   const double fill = (double)H * W / ((double)evf_cdiv(H, T_ROWS) * T_ROWS * evf_cdiv(W, T_COLS) * T_COLS);
@@ -291,16 +230,9 @@ int evf_conv3_b3t_launch(const float* src, int lds, const void* wp, const float*
   // channels at 256 x 256: 3 x 64 -> 2 x 64 + 32)
   const int rem = N % 64;
   const bool tail32 = N > 64 && rem > 0 && rem <= 32;
-  static bool once2 = false, once1 = false;
   const size_t smem2 = 3 * T_PLANE + 2 * 27 * 1024, smem1 = 3 * T_PLANE + 27 * 1024;
-  if (!once2) {
-    (void)hipFuncSetAttribute((const void*)k_conv3_b3t<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-    once2 = true;
-  }
-  if (!once1) {
-    (void)hipFuncSetAttribute((const void*)k_conv3_b3t<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1);
-    once1 = true;
-  }
+  evf_dynamic_lds_once<k_conv3_b3t<2>>(smem2);
+  evf_dynamic_lds_once<k_conv3_b3t<1>>(smem1);
   if (tail32) {
     hipLaunchKernelGGL((k_conv3_b3t<2>), dim3(gx, N / 64, ksplit), dim3(512), smem2, st, src, (const uint4*)wp, bias, out, g, accumulate,
                        ksplit);

@@ -187,6 +187,53 @@ def test_conv2d_b3_bias_and_accumulate_through_every_kernel(case, conv_mode):
     close(N(gx), (xr.grad.permute(0, 2, 3, 1) + gx0.double()).numpy(), 1e-5, "dgrad accumulate")
 
 
+@pytest.mark.parametrize("conv_mode", ["b3tile", "b3tilesplit"], indirect=True)
+@pytest.mark.parametrize("case", [(2, 32, 132, 24, 40), (1, 64, 260, 19, 33), (1, 20, 96, 9, 70)])
+def test_nstream_and_tile_kernels_give_the_same_bits(case, conv_mode, monkeypatch):
+    """k_conv3_b3n and k_conv3_b3t share their staging, the order of their products and their split-K ranges
+    (csrc/evf_conv_b3_family.h), and add the channel groups of an output element in index order: the same product gives the same
+    BITS through either, unsplit and with the contraction split (forced 3, which two channel groups make 2).  Cases (B, K
+    contraction channels, N output channels, H, W): five N tiles with a 4-channel remainder and ragged 8 x 32 / 16 x 32 tiles; nine
+    N tiles = two chunks of 5 + 4; a ragged last channel group.  Forward and input-gradient direction, real-valued (six-term) and
+    spike-valued (three-term) input, overwrite (with bias where the entry point has one) and accumulate.  None of the cases is a
+    shape the N-streaming kernel's own plan takes (12, 12 and 6 blocks), so the b3tile modes run the tile kernel."""
+    B, K, Nc, H, W = case
+    gen = torch.Generator().manual_seed(K + Nc)
+    L = _lib.load()
+    real = torch.randn(B, H, W, K, generator=gen)
+    spikes = torch.randint(0, 3, (B, H, W, K), generator=gen).float() * (torch.rand(B, H, W, K, generator=gen) < 0.3)
+    bias, base = G(torch.randn(Nc, generator=gen).numpy()), G(torch.randn(B, H, W, Nc, generator=gen).numpy())
+    packed = {}
+    for tr in (0, 1):  # forward: w [Cout = N][Cin = K]; input gradient: w [Cout = K][Cin = N], packed transposed
+        Cout, Cin = (K, Nc) if tr else (Nc, K)
+        w = G((torch.randn(Cout, Cin, 3, 3, generator=gen) * 0.2).numpy())
+        packed[tr] = torch.empty(L.evf_conv2d_b3_packed_size(Cout, Cin, 3, tr), device=DEV)
+        _lib.call("evf_pack_conv2d_weight_b3", _lib.ptr(w), Cout, Cin, 3, tr, Cin, 0, _lib.ptr(packed[tr]))
+    nws = L.evf_conv2d_b3_ws(B, H, W, Nc)
+    assert nws >= 3 * B * H * W * Nc  # (the forced split has its slabs)
+    ws = torch.empty(nws, device=DEV)
+
+    def products():
+        out = {}
+        for xname, x in (("real", G(real.numpy())), ("spikes", G(spikes.numpy()))):
+            for acc in (0, 1):
+                y = base.clone()
+                _lib.call("evf_conv2d_fwd_b3", _lib.ptr(x), K, _lib.ptr(packed[0]), None if acc else _lib.ptr(bias), _lib.ptr(y), Nc, B, H, W, K,
+                          Nc, 3, 1, acc, _lib.ptr(ws), nws)
+                out["fwd", xname, acc] = N(y)
+                y = base.clone()
+                _lib.call("evf_conv2d_dgrad_b3", _lib.ptr(x), K, _lib.ptr(packed[1]), _lib.ptr(y), Nc, B, H, W, Nc, K, 3, 1, acc, _lib.ptr(ws), nws)
+                out["dgrad", xname, acc] = N(y)
+        return out
+
+    tile = products()
+    monkeypatch.setenv("EVF_CONV_NSTREAM", "2")  # (the conv_mode fixture's b3nstream modes: the N-streaming kernel wherever it can run)
+    nstream = products()
+    for key in tile:
+        assert np.isfinite(tile[key]).all() and not np.array_equal(tile[key], N(base)), key
+        assert np.array_equal(tile[key], nstream[key]), (key, float(np.abs(tile[key] - nstream[key]).max()))
+
+
 @pytest.mark.parametrize("case", [(2, 128, 64, 16, 16), (1, 64, 64, 32, 40), (2, 36, 32, 17, 23), (1, 512, 128, 8, 8), (8, 512, 512, 16, 16),
                                   (2, 64, 130, 24, 24)])
 def test_wgrad_fused_slab_reduction_equals_the_three_launch_path(case, monkeypatch):
