@@ -38,6 +38,11 @@ SIGNATURES = {
     "evf_cm_loss_fwd_det": [P, P, P, P, P, I, I, I, I, I, I, F, F, I, P, P, P, P, P, L, P],
     "evf_cm_loss_bwd_ws_det": [I, I, I, I, I, I, I],
     "evf_cm_loss_bwd_det": [P, P, P, P, P, I, I, I, I, I, I, F, F, I, P, P, P, P, P, P, L, P],
+    # the deterministic voxel binning and IWE splat: the default calls' arguments (evf_iwe_splat_det: tau_bound before out)
+    "evf_splat_det_bits": [L, F],
+    "evf_encode_events_det": [P, I, I, I, I, I, I, P, P, P, P, P],
+    "evf_encode_window_det": [P, I, I, I, I, I, I, I, I, P, P, P],
+    "evf_iwe_splat_det": [P, P, P, P, P, P, I, I, I, I, I, F, F, F, I, I, F, P, P],
     "evf_image_variance": [P, I, I, P, P],
     "evf_avg_ts_ratio": [P, I, I, F, P, P],
     "evf_aee": [P, P, P, P, I, I, I, F, P, P],
@@ -183,13 +188,15 @@ SIGNATURES.update(NETWORK_SIGNATURES)
 _lib = None
 
 # Deterministic mode (EVF_DETERMINISTIC=1 at import, set_deterministic): the contrast-maximisation loss goes through
-# evf_cm_loss_fwd_det / evf_cm_loss_bwd_det (exact, order-independent sums) instead of the float atomics.  A switch of this
+# evf_cm_loss_fwd_det / evf_cm_loss_bwd_det, voxel grids through evf_encode_events_det / evf_encode_window_det and every
+# iwe_splat through evf_iwe_splat_det (exact, order-independent sums) instead of the float atomics.  A switch of this
 # module, not of the library: the C ABI has one entry point per form.
 _deterministic = os.environ.get("EVF_DETERMINISTIC", "0") == "1"
 
 
 def set_deterministic(on):
-    """Route the contrast-maximisation loss through its deterministic entry points (True) or the default ones (False)."""
+    """Route the contrast-maximisation loss, the voxel binning and the IWE splats through their deterministic entry points
+    (True) or the default ones (False)."""
     global _deterministic
     _deterministic = bool(on)
 
@@ -200,6 +207,25 @@ def deterministic():
 
 class EvflowError(RuntimeError):
     pass
+
+
+SPLAT_DET_SLOTS = 16384  # 64-bit slots of a stripe of the deterministic voxel / IWE kernels (128 KiB of LDS)
+
+
+def splat_det_refusal(terms, bound, planes, W, samples):
+    """Why evf_encode_*_det / evf_iwe_splat_det do not serve this shape (None: they do): `terms` events per sample with terms of
+    magnitude <= bound, `planes` image planes of width W per sample.  Asks the library's own bit rule; nothing is launched."""
+    if planes * W > SPLAT_DET_SLOTS:
+        return (f"{planes} planes x {W} pixels = {planes * W} slots per image row: a stripe row of 64-bit slots fits the LDS up to "
+                f"{SPLAT_DET_SLOTS}")
+    if samples > 65535:
+        return f"{samples} samples in one call (the limit is 65535)"
+    if terms > 0:
+        k = load().evf_splat_det_bits(int(terms), float(bound))
+        if k < 0:
+            return (f"{terms} events x a term bound of {bound} (>= 2^30, or not a finite non-negative bound) leaves fewer than 32 "
+                    "fraction bits for the exact sums")
+    return None
 
 
 def load():
@@ -341,7 +367,7 @@ def raw(name, *args):
 _DEFER_SAFE_FWD = {"evf_conv_lif_fwd_b3", "evf_conv_lif_fwd_b3_pred", "evf_head_lif_fwd", "evf_fwd_defer_flush",
                    "evf_conv_plif_fwd_b3", "evf_conv_plif_fwd_b3_pred",
                    "evf_head_plif_fwd",  # (recorded like evf_head_lif_fwd: the window's passes in one launch)
-                   "evf_encode_window", "evf_encode_events", "evf_events_to_image"}
+                   "evf_encode_window", "evf_encode_events", "evf_events_to_image", "evf_encode_window_det", "evf_encode_events_det"}
 # backward recording (evf_bwd_defer_*): these record themselves, or flush inside the library when they cannot
 _DEFER_SAFE_BWD = {"evf_lif_bwd_wgrad", "evf_lif_bwd_wgrad2", "evf_lif_bwd_wgrad_top", "evf_plif_bwd_wgrad2", "evf_plif_bwd_wgrad_top", "evf_conv_dgrad_b3_f32",
                    "evf_conv_dgrad_b3_f32_pair", "evf_conv_dgrad_b3", "evf_conv_dgrad_b3_pair", "evf_head_lif_bwd_wgrad", "evf_head_plif_bwd_wgrad",

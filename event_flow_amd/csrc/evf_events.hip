@@ -1229,9 +1229,14 @@ extern "C" int evf_cm_loss_fwd(const float* flow, const float* ev, const float* 
 // on its data.  The stripes hold 8-byte slots, i.e. half the rows of k_cm_splat_lds; the pre-pass and the scan are that kernel's.
 // A term is |wt * pol| <= 1 or |wt * tau * pol| <= P for polarity weights in [-1, 1] and event times in [0, 1] within a pass, a
 // pixel receives at most one tap of each of the M events: |sum * 2^k| <= M * P * 2^k < 2^62.
-static int cm_det_scale_log2(int M, int P) {  // the largest k with M * max(P, 1) * 2^k < 2^62
-  const unsigned long long n = (unsigned long long)M * (unsigned long long)(P > 1 ? P : 1);
+// THE bit rule of every fixed-point sum of this file: the largest k with terms * ceil(max(bound, 1)) * 2^k < 2^62, for `terms` terms per
+// slot of magnitude <= bound each.  Callers keep terms and ceil(bound) below 2^31 (anything beyond is refused for k < 32 anyway).
+static int det_scale_log2(unsigned long long terms, unsigned long long bound) {
+  const unsigned long long n = (terms > 1 ? terms : 1) * (bound > 1 ? bound : 1);
   return 61 - (63 - __builtin_clzll(n));
+}
+static int cm_det_scale_log2(int M, int P) {  // the largest k with M * max(P, 1) * 2^k < 2^62
+  return det_scale_log2((unsigned long long)M, (unsigned long long)(P > 1 ? P : 1));
 }
 #define CM_DET_MIN_LOG2 32  // fewer fraction bits than this: refused (M * P >= 2^30)
 static int cm_det_rows(int S, int B, int H, int W) {
@@ -1420,6 +1425,268 @@ extern "C" int evf_cm_loss_fwd_det(const float* flow, const float* ev, const flo
   const CmFin fin{stats, ticket, smooth_part, loss, S, Pm, srows * Pm * B, overwrite ? 4 : 5, (flags & 4) ? 1 : 0, regul_weight};
   hipLaunchKernelGGL(k_cm_splat_det, dim3(nst, S * B * 2), dim3(1024), lds, st, (const float4*)warp, tabs, ys, B, M, H, W, rows,
                      (float)P, cm_det_scale_log2(M, P), images, slots, fin);
+  return evf_status();
+}
+
+// ---- the deterministic forms of the voxel binning and of the IWE splat (evf_encode_*_det, evf_iwe_splat_det) ---------------------
+// The technique of k_cm_splat_det for the two other float-atomic sums whose terms have a bound known from the call's shape: a block
+// owns a stripe of rows of ONE sample, all planes, as signed 64-bit LDS slots; it scans that sample's events (L2 resident), computes
+// every term in fp32 exactly as the default kernel does, scales it by 2^k (ldexpf: exact), rounds ONCE (__float2ll_rn) and adds with
+// the 64-bit LDS integer atomic; the stripe is converted once and stored coalesced.  No zero-fill launch, no global atomic, no
+// ticket, no workspace.  k = det_scale_log2(terms per slot, bound of a term): shape and declared bounds, never data.
+#define SPLAT_DET_SLOTS 16384  // 64-bit slots of a stripe: 128 KiB of LDS
+
+extern "C" int evf_splat_det_bits(int64_t terms_per_slot, float bound) {
+  if (terms_per_slot <= 0 || !(bound >= 0.f) || !(bound < INFINITY)) return EVF_EINVAL;
+  const float cb = ceilf(bound > 1.f ? bound : 1.f);
+  if (terms_per_slot >= (1ll << 30) || cb >= 1073741824.f) return EVF_ENOTSUP;  // (k < 32 whatever the other factor)
+  const int k = det_scale_log2((unsigned long long)terms_per_slot, (unsigned long long)cb);
+  return k >= CM_DET_MIN_LOG2 ? k : EVF_ENOTSUP;
+}
+
+// rows of a stripe of `planes` planes of width W: what the LDS holds, capped at H, halved while above 8 and the grid is short of
+// blocks (the rule of cm_det_rows); 0: a single row does not fit
+static int splat_det_rows(int samples, int planes, int H, int W) {
+  if ((long)planes * W > SPLAT_DET_SLOTS) return 0;
+  int rows = SPLAT_DET_SLOTS / (planes * W);
+  if (rows > H) rows = H;
+  while (rows > 8 && (long)samples * evf_cdiv(H, rows) < 512) rows >>= 1;
+  return rows;
+}
+
+// the stripe's sums -> floats, every sum converted ONCE: planes [nplanes][H*W] of one sample at `o`, rows r0 .. r0 + nr
+__device__ __forceinline__ void det_stripe_out(const unsigned long long* __restrict__ img, int nplanes, int plane, int n, int k2,
+                                               float* __restrict__ o, long HW) {
+  for (int c = 0; c < nplanes; ++c)
+    for (int q = threadIdx.x; q < n; q += blockDim.x) o[c * HW + q] = ldexpf(__ll2float_rn((long long)img[c * plane + q]), -k2);
+}
+
+// Voxel grid of k_encode_events / k_encode_window (dataloader/encodings.py:48-67).  Sample blockIdx.y = b * P + pp of ev [B][P][N]
+// goes to plane set pp * B + b of voxel (P = 1: batch-major [B][nb][H][W]; else pass-major [P][B][nb][H][W]).  An event belongs to
+// the stripe that holds its row; a slot receives at most one term p * w per event, |p * w| <= 1 for |p| <= 1.
+__global__ __launch_bounds__(1024) void k_voxel_det(const float4* __restrict__ ev, int B, int P, int N, int H, int W, int nb,
+                                                    int round_ts, int rows, int k2, float* __restrict__ voxel) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  unsigned long long* img = (unsigned long long*)smem_raw;  // [nb][rows*W] two's complement
+  const int bp = blockIdx.y, b = bp / P, pp = bp - b * P;
+  const int r0 = blockIdx.x * rows, nr = min(rows, H - r0), plane = rows * W;
+  for (int q = threadIdx.x; q < nb * plane; q += blockDim.x) img[q] = 0ull;
+  __syncthreads();
+  const float4* __restrict__ e4 = ev + (long)bp * N;
+  const float lo = (float)r0, hi = (float)(r0 + nr), fW = (float)W;
+  for (int i = threadIdx.x; i < N; i += blockDim.x) {
+    const float4 e = e4[i];  // (t, y, x, p)
+    const float p = e.w;
+    if (p == 0.f) continue;  // padding
+    const float ty = truncf(e.y), tx = truncf(e.z);  // .long() truncates toward zero
+    if (!(ty >= lo && ty < hi && tx >= 0.f && tx < fW)) continue;  // other stripes / outside the image (NaN too)
+    unsigned long long* px = img + ((int)ty - r0) * W + (int)tx;
+    float t = e.x * (float)(nb - 1);
+    if (round_ts) t = rintf(t);
+    for (int k = 0; k < nb; ++k) {
+      const float w = fmaxf(0.f, 1.0f - fabsf(t - (float)k));
+      if (w != 0.f) atomicAdd(px + k * plane, (unsigned long long)__float2ll_rn(ldexpf(p * w, k2)));
+    }
+  }
+  __syncthreads();
+  const long HW = (long)H * W;
+  det_stripe_out(img, nb, plane, nr * W, k2, voxel + ((long)pp * B + b) * nb * HW + (long)r0 * W, HW);
+}
+
+// the refusals and the launch of k_voxel_det, shared by the two entry points; `samples` = B * P
+static int voxel_det_check(int samples, int N, int W, int nb) {
+  if ((long)nb * W > SPLAT_DET_SLOTS || samples > 65535) return EVF_ENOTSUP;
+  const int k2 = evf_splat_det_bits(N, 1.0f);
+  return k2 < 0 ? EVF_ENOTSUP : EVF_OK;
+}
+static void voxel_det_launch(const float* ev, int B, int P, int N, int H, int W, int nb, int round_ts, float* voxel, hipStream_t st) {
+  const int rows = splat_det_rows(B * P, nb, H, W);
+  const size_t lds = (size_t)nb * rows * W * sizeof(unsigned long long);
+  evf_dynamic_lds_once<k_voxel_det>(SPLAT_DET_SLOTS * sizeof(unsigned long long));
+  hipLaunchKernelGGL(k_voxel_det, dim3(evf_cdiv(H, rows), B * P), dim3(1024), lds, st, (const float4*)ev, B, P, N, H, W, nb, round_ts,
+                     rows, evf_splat_det_bits(N, 1.0f), voxel);
+}
+
+extern "C" int evf_encode_events_det(const float* ev, int B, int N, int H, int W, int num_bins, int round_ts, float* cnt, float* mask,
+                                     float* voxel, float* pol, void* stream) {
+  if (!ev || B <= 0 || N < 0 || H <= 0 || W <= 0 || (voxel && num_bins < 1)) return EVF_EINVAL;
+  if (voxel && N > 0) {
+    const int rc = voxel_det_check(B, N, W, num_bins);
+    if (rc) return rc;
+  }
+  hipStream_t st = EVF_STREAM(stream);
+  const size_t HW = (size_t)H * W;
+  int rc = 0;
+  if (cnt) rc |= evf_hip(evf_memset_async(cnt, 0, sizeof(float) * B * 2 * HW, st));
+  if (mask) rc |= evf_hip(evf_memset_async(mask, 0, sizeof(float) * B * HW, st));
+  if (voxel && N == 0) rc |= evf_hip(evf_memset_async(voxel, 0, sizeof(float) * B * num_bins * HW, st));
+  if (rc || N == 0) return rc;
+  // cnt / mask / pol: integer-valued sums or plain stores -- the default kernel, without its voxel part
+  if (cnt || mask || pol)
+    hipLaunchKernelGGL(k_encode_events, dim3(evf_cdiv((long)B * N, 256)), dim3(256), 0, st, (const float4*)ev, B, N, H, W, num_bins,
+                       round_ts, cnt, mask, (float*)nullptr, (float2*)pol);
+  if (voxel) voxel_det_launch(ev, B, 1, N, H, W, num_bins, round_ts, voxel, st);
+  return evf_status();
+}
+
+extern "C" int evf_encode_window_det(const float* ev, int B, int P, int N, int H, int W, int num_bins, int round_ts, int want,
+                                     float* dense, float* pol, void* stream) {
+  if ((N > 0 && !ev) || B <= 0 || P <= 0 || N < 0 || H <= 0 || W <= 0 || ((want & 2) && num_bins < 1) || ((want & 7) && !dense))
+    return EVF_EINVAL;
+  if ((want & 2) && N > 0) {
+    const int rc = (long)B * P > 65535 ? EVF_ENOTSUP : voxel_det_check(B * P, N, W, num_bins);
+    if (rc) return rc;
+  }
+  hipStream_t st = EVF_STREAM(stream);
+  const size_t HW = (size_t)H * W, S = (size_t)B * P;
+  const size_t n_cnt = (want & 1) ? S * 2 * HW : 0, n_vox = (want & 2) ? S * num_bins * HW : 0, n_mask = (want & 4) ? S * HW : 0;
+  float* cnt = n_cnt ? dense : nullptr;
+  float* voxel = n_vox ? dense + n_cnt : nullptr;
+  float* mask = n_mask ? dense + n_cnt + n_vox : nullptr;
+  int rc = 0;
+  if (N == 0) return (n_cnt + n_vox + n_mask) ? evf_hip(evf_memset_async(dense, 0, sizeof(float) * (n_cnt + n_vox + n_mask), st)) : EVF_OK;
+  if (cnt) rc |= evf_hip(evf_memset_async(cnt, 0, sizeof(float) * n_cnt, st));  // (the voxel part is written whole by its kernel)
+  if (mask) rc |= evf_hip(evf_memset_async(mask, 0, sizeof(float) * n_mask, st));
+  if (rc) return rc;
+  if (cnt || mask || pol)
+    hipLaunchKernelGGL(k_encode_window, dim3(evf_cdiv((long)B * P * N, 256)), dim3(256), 0, st, (const float4*)ev, B, P, N, H, W,
+                       num_bins, round_ts, cnt, mask, (float*)nullptr, (float2*)pol);
+  if (voxel) voxel_det_launch(ev, B, P, N, H, W, num_bins, round_ts, voxel, st);
+  return evf_status();
+}
+
+// evf_iwe_splat for every mode / nch / map_of_event / ts_shift / weight combination: per event the flow gather, `flow * 0`, the
+// warp and the taps and products of evf_splat<ROUND>, term for term; only the accumulation differs.  A pixel receives at most one
+// tap of an event, so a slot holds at most M terms: |w * a| <= 1 for weights in [-1, 1], |w * tau * a| <= tau_bound.  The warped
+// row(s) decide whether an event is this stripe's.  Taps with non-finite coordinates are skipped (the default path lets NaN into
+// the image: non-finite flow is outside this mode's contract), and so is an event whose own pixel lies outside the flow map (the
+// default path reads out of bounds there).
+template <bool ROUND>
+__global__ __launch_bounds__(1024) void k_iwe_splat_det(const float* __restrict__ flow, const float4* __restrict__ ev,
+                                                        const int32_t* __restrict__ map_of_event,
+                                                        const int32_t* __restrict__ ts_shift, const float* __restrict__ w0,
+                                                        const float* __restrict__ w1, int wstride, int B, int M, int H, int W,
+                                                        float S, float tref, float tref_ts, int mode, int nch, int rows, int k2,
+                                                        float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  unsigned long long* img = (unsigned long long*)smem_raw;  // [nch][rows*W] two's complement
+  const int b = blockIdx.y, r0 = blockIdx.x * rows;
+  const int nr = min(rows, H - r0), plane = rows * W;
+  for (int q = threadIdx.x; q < nch * plane; q += blockDim.x) img[q] = 0ull;
+  __syncthreads();
+  const long HW = (long)H * W;
+  const float lo = (float)r0, hi = (float)(r0 + nr), fW = (float)W;
+  auto put = [&](unsigned long long* px, float v) {
+    if (v != 0.f) atomicAdd(px, (unsigned long long)__float2ll_rn(ldexpf(v, k2)));
+  };
+#define IWD_U 4  // (events in batches, as in k_iwe_splat_lds: the event loads, then the gathers that depend on them)
+  for (int e0 = threadIdx.x; e0 < M; e0 += IWD_U * blockDim.x) {
+    float4 qs[IWD_U];
+    float ts[IWD_U], fys[IWD_U], fxs[IWD_U];
+    bool ok[IWD_U];
+#pragma unroll
+    for (int u = 0; u < IWD_U; ++u) {
+      const int e = min(e0 + u * (int)blockDim.x, M - 1);  // clamped: loads stay unconditional
+      qs[u] = ev[(long)b * M + e];
+      ts[u] = ts_shift ? (float)ts_shift[e] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < IWD_U; ++u) {
+      const int e = min(e0 + u * (int)blockDim.x, M - 1);
+      const float lin = qs[u].y * fW + qs[u].z;  // the index of evf_event_flow, checked before it is used
+      ok[u] = e0 + u * (int)blockDim.x < M && lin > -1.0f && lin < (float)HW;
+      fys[u] = fxs[u] = 0.f;
+      if (ok[u]) evf_event_flow(flow, map_of_event ? map_of_event[e] : 0, B, b, HW, qs[u].y, qs[u].z, W, fys[u], fxs[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < IWD_U; ++u) {
+      if (!ok[u]) continue;
+      const float4 q = qs[u];
+      const float t = q.x + ts[u];
+      float fy = fys[u], fx = fxs[u];
+      if (mode & 2) {  // `flow * 0`
+        fy *= 0.f;
+        fx *= 0.f;
+      }
+      const float tau = (mode & 8) ? (tref_ts - t) : t;
+      const Warp w = evf_warp(t, q.y, q.z, fy, fx, tref, S);
+      const long i = (long)b * M + e0 + u * (int)blockDim.x;
+      if (ROUND) {
+        const float iy = rintf(w.wy), ix = rintf(w.wx);
+        if (!(iy >= lo && iy < hi && ix >= 0.f && ix < fW)) continue;  // other stripes / outside (NaN too)
+        const float a0 = w0 ? w0[i * wstride] : 1.0f;
+        const float a1 = w1 ? w1[i * wstride] : 0.0f;
+        unsigned long long* px = img + ((int)iy - r0) * W + (int)ix;
+        put(px, a0);
+        if (nch >= 2) put(px + plane, a1);
+        if (nch == 4) {
+          put(px + 2 * plane, tau * a0);
+          put(px + 3 * plane, tau * a1);
+        }
+      } else {
+        const float cy[2] = {floorf(w.wy), floorf(w.wy + 1.0f)};
+        const float cx[2] = {floorf(w.wx), floorf(w.wx + 1.0f)};
+        if (!((cy[0] >= lo && cy[0] < hi) || (cy[1] >= lo && cy[1] < hi))) continue;
+        const float a0 = w0 ? w0[i * wstride] : 1.0f;
+        const float a1 = w1 ? w1[i * wstride] : 0.0f;
+        float ay[2], ax[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          ay[k] = fmaxf(0.f, 1.0f - fabsf(w.wy - cy[k]));
+          ax[k] = fmaxf(0.f, 1.0f - fabsf(w.wx - cx[k]));
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            if (!(cy[j] >= lo && cy[j] < hi && cx[k] >= 0.f && cx[k] < fW)) continue;
+            const float wt = ay[j] * ax[k];
+            if (wt == 0.f) continue;
+            unsigned long long* px = img + ((int)cy[j] - r0) * W + (int)cx[k];
+            put(px, wt * a0);
+            if (nch >= 2) put(px + plane, wt * a1);
+            if (nch == 4) {
+              const float wtau = wt * tau;
+              put(px + 2 * plane, wtau * a0);
+              put(px + 3 * plane, wtau * a1);
+            }
+          }
+      }
+    }
+  }
+#undef IWD_U
+  __syncthreads();
+  det_stripe_out(img, nch, plane, nr * W, k2, out + (long)b * nch * HW + (long)r0 * W, HW);
+}
+
+extern "C" int evf_iwe_splat_det(const float* flow, const float* ev, const int32_t* map_of_event, const int32_t* ts_shift,
+                                 const float* w0, const float* w1, int wstride, int B, int M, int H, int W, float flow_scaling,
+                                 float tref, float tref_ts, int mode, int nch, float tau_bound, float* out, void* stream) {
+  if (!flow || !out || B <= 0 || M < 0 || H <= 0 || W <= 0 || (nch != 1 && nch != 2 && nch != 4)) return EVF_EINVAL;
+  if (nch == 4 && !(mode & 4)) return EVF_EINVAL;
+  if (M > 0 && !ev) return EVF_EINVAL;
+  if ((long)H * W >= (1l << 24)) return EVF_ENOTSUP;  // (pixel indices are exact floats below 2^24)
+  int k2 = 0;
+  if (M > 0) {
+    if ((long)nch * W > SPLAT_DET_SLOTS || B > 65535) return EVF_ENOTSUP;
+    k2 = evf_splat_det_bits(M, nch == 4 ? tau_bound : 1.0f);
+    if (k2 == EVF_EINVAL) return EVF_EINVAL;
+    if (k2 < 0) return EVF_ENOTSUP;
+  }
+  hipStream_t st = EVF_STREAM(stream);
+  if (M == 0) return evf_hip(evf_memset_async(out, 0, sizeof(float) * (size_t)B * nch * H * W, st));
+  const int rows = splat_det_rows(B, nch, H, W);
+  const size_t lds = (size_t)nch * rows * W * sizeof(unsigned long long);
+  dim3 grid(evf_cdiv(H, rows), B), block(1024);
+  if (mode & 1) {
+    evf_dynamic_lds_once<k_iwe_splat_det<true>>(SPLAT_DET_SLOTS * sizeof(unsigned long long));
+    hipLaunchKernelGGL(k_iwe_splat_det<true>, grid, block, lds, st, flow, (const float4*)ev, map_of_event, ts_shift, w0, w1, wstride,
+                       B, M, H, W, flow_scaling, tref, tref_ts, mode, nch, rows, k2, out);
+  } else {
+    evf_dynamic_lds_once<k_iwe_splat_det<false>>(SPLAT_DET_SLOTS * sizeof(unsigned long long));
+    hipLaunchKernelGGL(k_iwe_splat_det<false>, grid, block, lds, st, flow, (const float4*)ev, map_of_event, ts_shift, w0, w1, wstride,
+                       B, M, H, W, flow_scaling, tref, tref_ts, mode, nch, rows, k2, out);
+  }
   return evf_status();
 }
 

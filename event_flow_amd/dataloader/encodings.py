@@ -3,6 +3,8 @@ dataloader/encodings.py (same function names, arguments and error behaviour).
 
 The arithmetic runs in libevflow_hip.so (`evf_events_to_image`,
 `evf_encode_events`); tensors must live on the GPU -- there is no CPU path.
+In deterministic mode (`_lib.set_deterministic`) calls that produce a voxel
+grid go through `evf_encode_events_det` / `evf_encode_window_det`.
 `encode_event_list` is the batched entry point the training loop uses instead
 of the reference's per-sample CPU loop (dataloader/h5.py:282-286)."""
 
@@ -13,6 +15,18 @@ from .. import _lib
 
 def _f32(t):
     return t.to(torch.float32).contiguous()
+
+
+def _encode_entry(name, voxel, N, num_bins, W, samples):
+    """The entry point of a binning call: `name`, or `name`_det in deterministic mode when a voxel grid is among the outputs
+    (cnt / mask / pol are exact in either form).  A shape the deterministic form refuses raises -- never the atomics instead."""
+    if not (voxel and _lib.deterministic()):
+        return name
+    why = _lib.splat_det_refusal(N, 1.0, int(num_bins), W, samples)
+    if why:
+        raise _lib.EvflowError(f"deterministic voxel binning not supported: {why} "
+                               "(set_deterministic(False) / EVF_DETERMINISTIC=0 selects the float-atomic path)")
+    return name + "_det"
 
 
 def events_to_image(xs, ys, ps, sensor_size=(180, 240), accumulate=True):
@@ -38,8 +52,8 @@ def events_to_voxel(xs, ys, ts, ps, num_bins, sensor_size=(180, 240), round_ts=F
     H, W = int(sensor_size[0]), int(sensor_size[1])
     ev = _event_rows(xs, ys, ts, ps)
     voxel = torch.empty((1, num_bins, H, W), dtype=torch.float32, device=xs.device)
-    _lib.call("evf_encode_events", _lib.ptr(ev), 1, ev.shape[1], H, W, int(num_bins), 1 if round_ts else 0, None, None,
-              _lib.ptr(voxel), None)
+    _lib.call(_encode_entry("evf_encode_events", True, ev.shape[1], num_bins, W, 1), _lib.ptr(ev), 1, ev.shape[1], H, W,
+              int(num_bins), 1 if round_ts else 0, None, None, _lib.ptr(voxel), None)
     return voxel[0]
 
 
@@ -69,8 +83,8 @@ def encode_event_list(event_list, num_bins, sensor_size, round_ts=False, want=("
     mask = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev) if "mask" in want else None
     voxel = torch.empty((B, num_bins, H, W), dtype=torch.float32, device=dev) if "voxel" in want else None
     pol = torch.empty((B, N, 2), dtype=torch.float32, device=dev) if "pol" in want else None
-    _lib.call("evf_encode_events", _lib.ptr(ev), B, N, H, W, int(num_bins), 1 if round_ts else 0, _lib.ptr(cnt),
-              _lib.ptr(mask), _lib.ptr(voxel), _lib.ptr(pol))
+    _lib.call(_encode_entry("evf_encode_events", voxel is not None, N, num_bins, W, B), _lib.ptr(ev), B, N, H, W, int(num_bins),
+              1 if round_ts else 0, _lib.ptr(cnt), _lib.ptr(mask), _lib.ptr(voxel), _lib.ptr(pol))
     if cnt is not None:
         out["event_cnt"] = cnt
     if mask is not None:
@@ -124,8 +138,8 @@ def encode_window(ev, num_bins, sensor_size, round_ts=False, want=("cnt", "mask"
     dense = torch.empty(max(n_cnt + n_vox + n_mask, 1), dtype=torch.float32, device=dev)
     pol = torch.empty((B, P, N, 2), dtype=torch.float32, device=dev) if "pol" in want else None
     flags = (1 if n_cnt else 0) | (2 if n_vox else 0) | (4 if n_mask else 0)
-    _lib.call("evf_encode_window", _lib.ptr(ev), B, P, N, H, W, int(num_bins), 1 if round_ts else 0, flags,
-              _lib.ptr(dense) if flags else None, _lib.ptr(pol))
+    _lib.call(_encode_entry("evf_encode_window", n_vox > 0, N, num_bins, W, B * P), _lib.ptr(ev), B, P, N, H, W, int(num_bins),
+              1 if round_ts else 0, flags, _lib.ptr(dense) if flags else None, _lib.ptr(pol))
     cnt = dense[:n_cnt].view(P, B, 2, H, W) if n_cnt else None
     vox = dense[n_cnt:n_cnt + n_vox].view(P, B, num_bins, H, W) if n_vox else None
     mask = dense[n_cnt + n_vox:n_cnt + n_vox + n_mask].view(B, P, H, W) if n_mask else None

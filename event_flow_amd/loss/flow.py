@@ -14,9 +14,15 @@ Differences in mechanism, not in results:
     `EventWarping` through `evf_cm_loss_fwd_det` / `evf_cm_loss_bwd_det`: exact,
     order-independent sums instead of float atomics -- bit-identical from run to run.
     `EVF_CM_BWD_LDS`, `evf_cm_merge` and `CM_LDS_MIN_EVENTS` have no effect in that mode.
+    The same switch routes every `iwe_splat` (the images of `FWL`, `RSAT`, `compute_window_*`, `compute_pol_iwe`,
+    `deblur_events`) through `evf_iwe_splat_det` and voxel grids through `evf_encode_events_det` /
+    `evf_encode_window_det`: the fixed-point stripes of the loss, with k from `splat_det_bits`.  A shape
+    those refuse raises `EvflowError`; nothing falls back to the atomics.
 """
 
+import math
 import os
+import struct
 
 import torch
 
@@ -138,9 +144,18 @@ CM_LDS_MIN_EVENTS = int(os.environ.get("EVF_CM_LDS_MIN_EVENTS", 32768))
 CM_DET_MIN_LOG2 = 32  # deterministic mode: fewer fraction bits than this are refused (csrc/evf_events.hip)
 
 
+def splat_det_bits(terms_per_slot, bound):
+    """Mirror of the library's bit rule (evf_splat_det_bits without its refusals): k of a fixed-point sum of at most
+    `terms_per_slot` terms of magnitude <= `bound` (a float32) per slot, the largest integer with
+    terms_per_slot * ceil(max(bound, 1)) * 2^k < 2^62.  Fewer than CM_DET_MIN_LOG2 bits are refused by the entry points."""
+    b32 = struct.unpack("f", struct.pack("f", float(bound)))[0]
+    n = max(int(terms_per_slot), 1) * math.ceil(max(b32, 1.0))
+    return 61 - (n.bit_length() - 1)
+
+
 def cm_det_scale_log2(M, P):
     """k of the deterministic forward: the largest integer with M * max(P, 1) * 2^k < 2^62 (shape alone, never data)."""
-    return 61 - ((int(M) * max(int(P), 1)).bit_length() - 1)
+    return splat_det_bits(M, max(int(P), 1))
 
 
 def cm_det_grad_exp(max_bits, M):
@@ -388,7 +403,7 @@ class BaseValidationLoss(torch.nn.Module):
         w0 = polm[:, :, 0:1] if pol else None
         w1 = polm[:, :, 1:2] if pol else None
         return iwe_splat(maps, ev, self.res, self.flow_scaling, float(self._win.passes), round_idx=round_idx, w0=w0, w1=w1,
-                         nch=nch, zero_flow=zero_flow, with_ts=with_ts, map_of_event=moe, ts_shift=ev_pass)
+                         nch=nch, zero_flow=zero_flow, with_ts=with_ts, map_of_event=moe, ts_shift=ev_pass, passes=self._win.passes)
 
     def compute_window_events(self):
         """Per-polarity event count image of the window [B,2,H,W].  loss/flow.py:432-441."""

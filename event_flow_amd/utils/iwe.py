@@ -7,6 +7,9 @@ libevflow_hip.so; there is no CPU path.
 weights and the atomic scatter in one launch, nothing materialised.
 `get_interpolation` / `interpolate` / `purge_unfeasible` keep the reference's
 materialising API for callers that want the index / weight tensors.
+In deterministic mode `iwe_splat` (and everything built on it) sums exactly and
+order-independently through `evf_iwe_splat_det`; the materialising `interpolate`
+keeps its float atomics (its weights have no bound known from the shape).
 """
 
 import torch
@@ -69,9 +72,13 @@ def interpolate(idx, weights, res, polarity_mask=None):
 
 
 def iwe_splat(flow_maps, event_list, res, flow_scaling, tref, *, round_idx, w0=None, w1=None, nch=1, zero_flow=False,
-              with_ts=False, ts_from_tref=None, map_of_event=None, ts_shift=None):
+              with_ts=False, ts_from_tref=None, map_of_event=None, ts_shift=None, passes=None):
     """Thin wrapper over evf_iwe_splat (see include/evflow.h).  flow_maps is
-    [B,2,H,W] or [n_maps,B,2,H,W]."""
+    [B,2,H,W] or [n_maps,B,2,H,W].  In deterministic mode (`_lib.set_deterministic`)
+    it calls evf_iwe_splat_det; `passes` is then the number of passes the event
+    times span (t + ts_shift in [0, passes]; default: 1 without ts_shift, else
+    max(ts_shift) + 1, read back from the device), from which the bound of the
+    timestamp terms follows."""
     _lib.require_gpu(event_list, "iwe_splat")
     ev = _f32c(event_list)
     fl = _f32c(flow_maps)
@@ -84,6 +91,27 @@ def iwe_splat(flow_maps, event_list, res, flow_scaling, tref, *, round_idx, w0=N
         a1, s1 = a1.reshape(B, M).contiguous(), 1
     mode = (1 if round_idx else 0) | (2 if zero_flow else 0) | (4 if with_ts else 0) | (8 if ts_from_tref is not None else 0)
     out = torch.empty((B, nch, H, W), dtype=torch.float32, device=ev.device)
+    if _lib.deterministic():
+        tau_bound = 1.0
+        if nch == 4:
+            if passes is None:
+                passes = 1 if ts_shift is None or ts_shift.numel() == 0 else int(ts_shift.max()) + 1
+            tau_bound = float(passes)  # |t + shift| <= passes
+            if ts_from_tref is not None:  # tau = tref_ts - t
+                tau_bound = max(abs(float(ts_from_tref)), abs(float(ts_from_tref) - float(passes)))
+        why = _lib.splat_det_refusal(M, tau_bound, nch, W, B)
+        if why is None and H * W >= 1 << 24:
+            why = f"an image of {H} x {W} pixels (pixel indices must stay below 2^24)"
+        if why:  # never a silent fall-back to the atomics
+            raise _lib.EvflowError(f"deterministic IWE splat not supported: {why} "
+                                   "(set_deterministic(False) / EVF_DETERMINISTIC=0 selects the float-atomic path)")
+        _lib.call(
+            "evf_iwe_splat_det", _lib.ptr(fl), _lib.ptr(ev), _lib.ptr(map_of_event), _lib.ptr(ts_shift),
+            a0.data_ptr() if a0 is not None else None, a1.data_ptr() if a1 is not None else None, s0 if a0 is not None else s1,
+            B, M, H, W, float(flow_scaling), float(tref), float(ts_from_tref if ts_from_tref is not None else 0.0), mode, nch,
+            tau_bound, _lib.ptr(out),
+        )
+        return out
     _lib.call(
         "evf_iwe_splat", _lib.ptr(fl), _lib.ptr(ev), _lib.ptr(map_of_event), _lib.ptr(ts_shift),
         a0.data_ptr() if a0 is not None else None, a1.data_ptr() if a1 is not None else None, s0 if a0 is not None else s1,

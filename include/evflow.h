@@ -170,6 +170,36 @@ int evf_cm_loss_bwd_det(const float* flow, const float* ev, const float* pol, co
                         const float* images, const float* stats, const float* grad_out,
                         float* gimages, float* dflow, float* ws, int64_t ws_floats, void* stream);
 
+/* The DETERMINISTIC forms of evf_encode_events, evf_encode_window and evf_iwe_splat: the same per-event terms, summed with the
+ * 64-bit fixed-point LDS stripes of evf_cm_loss_fwd_det, so that every output is a function of the SET of events.  Chosen by
+ * calling them (Python: _lib.set_deterministic, environment EVF_DETERMINISTIC=1); no state in the library.
+ *  - evf_splat_det_bits: k of such a sum, the largest integer with terms_per_slot * ceil(max(bound, 1)) * 2^k < 2^62 -- shape and
+ *    declared bounds alone.  Returns k, EVF_ENOTSUP for k < 32, EVF_EINVAL for terms_per_slot <= 0 or a bound that is negative
+ *    or not finite.  No GPU work.  evf_cm_loss_fwd_det's k is evf_splat_det_bits(M, P).
+ *  - evf_encode_events_det / evf_encode_window_det: the arguments and layouts of the default calls.  voxel
+ *    (dataloader/encodings.py:48-67): one block per stripe of rows of a sample holds all num_bins planes; at most one term
+ *    p * w per event and slot, |p| <= 1 ASSUMED, so k = evf_splat_det_bits(N, 1).  cnt, mask, pol (dataloader/encodings.py:70-85,
+ *    dataloader/base.py:159-171, :210-222) are integer-valued sums or plain stores for p = +-1: zero-filled here and written by
+ *    the default kernel.  EVF_ENOTSUP when a voxel grid is requested and num_bins * W > 16384 (a stripe row of 64-bit slots
+ *    does not fit 128 KiB of LDS), B * P > 65535 or k < 32.
+ *  - evf_iwe_splat_det (utils/iwe.py:20-92): the arguments of evf_iwe_splat and tau_bound, the caller's bound of |tau| for the
+ *    w*tau images (nch = 4; ignored otherwise): the number of passes for tau = t + ts_shift with t in [0, 1], or
+ *    max(|tref_ts|, |tref_ts - P|) with mode & 8.  Weights in [-1, 1] ASSUMED (the reference's masks are 0 / 1); a pixel
+ *    receives at most one tap per event, so k = evf_splat_det_bits(M, nch == 4 ? tau_bound : 1).  Serves every mode / nch /
+ *    map_of_event / ts_shift / weight combination of evf_iwe_splat.  Taps with non-finite coordinates are skipped: non-finite
+ *    flow is outside this form's contract (evf_iwe_splat lets NaN into the image); an event whose own pixel lies outside the
+ *    flow map is skipped as well.  EVF_ENOTSUP for nch * W > 16384, B > 65535, H * W >= 2^24 or k < 32.
+ * Errors come before any launch; N == 0 / M == 0 zero-fills the outputs and returns EVF_OK. */
+int evf_splat_det_bits(int64_t terms_per_slot, float bound);
+int evf_encode_events_det(const float* ev, int B, int N, int H, int W, int num_bins, int round_ts,
+                          float* cnt, float* mask, float* voxel, float* pol, void* stream);
+int evf_encode_window_det(const float* ev, int B, int P, int N, int H, int W, int num_bins, int round_ts, int want,
+                          float* dense, float* pol, void* stream);
+int evf_iwe_splat_det(const float* flow, const float* ev, const int32_t* map_of_event, const int32_t* ts_shift,
+                      const float* w0, const float* w1, int wstride,
+                      int B, int M, int H, int W, float flow_scaling, float tref, float tref_ts,
+                      int mode, int nch, float tau_bound, float* out, void* stream);
+
 /* Per-sample reductions used by FWL / RSAT (loss/flow.py:481-579):
  *   evf_image_variance: unbiased variance over H*W of img [B,1,H,W] -> [B]
  *   evf_avg_ts_ratio  : images [B,4,H,W] (I_pos,I_neg,TS_pos,TS_neg) ->
