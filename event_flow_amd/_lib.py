@@ -134,6 +134,10 @@ NETWORK_SIGNATURES = {
     "evf_cm_merge": [I],
     "evf_cm_bwd_lds": [I],
     "evf_clip_adam_fused": [P, P, P, P, L, F, F, F, F, F, I, P, I, P],
+    "evf_clip_adam_fused_fits": [L, P],
+    # evf_clip_adam_step's arguments + the per-block partial sums of squares and their size in floats
+    "evf_clip_adam_det_ws": [L],
+    "evf_clip_adam_step_det": [P, P, P, P, L, F, F, F, F, F, I, P, I, P, L, P],
     "evf_grads_finalize": [P, P, I, I, P, I, P, I, I, P, I, I, I, P, P, P, P, I, P],
     # general path (any channel count, NHWC fp32)
     "evf_conv2d_packed_size": [I, I, I, I],
@@ -155,6 +159,9 @@ NETWORK_SIGNATURES = {
     "evf_conv2d_fwd_b3_parts": [P, I, P, P, I, I, I, I, I, I, I, I, I, P, L, P, P],
     "evf_lif_fwd_parts": [P, I, L, P, I, L, P, P, P, P, P, L, I, I, P, P, P, P],
     "evf_neuron_bwd": [I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, F, P, P, P, P, P, P, P, P, P, P, P],
+    # the deterministic form: evf_neuron_bwd's arguments, ws followed by its size in floats
+    "evf_neuron_bwd_det_ws": [L, I, I],
+    "evf_neuron_bwd_det": [I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, F, P, P, P, P, P, P, P, P, P, P, L, P],
     "evf_pretrace_fwd": [P, I, I, I, I, I, I, I, P, P, P],
     "evf_pretrace_bwd": [P, I, P, I, I, I, I, I, I, P, I, I, P],
     "evf_concat_channels": [P, P, P, I, L, P, I, P],
@@ -182,21 +189,27 @@ NETWORK_SIGNATURES = {
     "evf_gru_out_bwd": [P, P, P, P, L, P, P, P, P],
     "evf_gru_gates_bwd": [P, P, P, L, P, P, P],
 }
-RESTYPES = {"evf_head1x1_ws": ctypes.c_int64, "evf_comm_last_error": ctypes.c_char_p, "evf_conv2d_packed_size": ctypes.c_int64, "evf_conv2d_b3_packed_size": ctypes.c_int64, "evf_conv2d_b3_ws": ctypes.c_int64, "evf_conv2d_wgrad_ws": ctypes.c_int64, "evf_cm_loss_ws": ctypes.c_int64, "evf_cm_loss_ws_det": ctypes.c_int64, "evf_cm_loss_bwd_ws_det": ctypes.c_int64}
+RESTYPES = {"evf_head1x1_ws": ctypes.c_int64, "evf_comm_last_error": ctypes.c_char_p, "evf_conv2d_packed_size": ctypes.c_int64, "evf_conv2d_b3_packed_size": ctypes.c_int64, "evf_conv2d_b3_ws": ctypes.c_int64, "evf_conv2d_wgrad_ws": ctypes.c_int64, "evf_cm_loss_ws": ctypes.c_int64, "evf_cm_loss_ws_det": ctypes.c_int64, "evf_cm_loss_bwd_ws_det": ctypes.c_int64,
+            "evf_neuron_bwd_det_ws": ctypes.c_int64, "evf_clip_adam_det_ws": ctypes.c_int64}
 SIGNATURES.update(NETWORK_SIGNATURES)
 
 _lib = None
 
 # Deterministic mode (EVF_DETERMINISTIC=1 at import, set_deterministic): the contrast-maximisation loss goes through
 # evf_cm_loss_fwd_det / evf_cm_loss_bwd_det, voxel grids through evf_encode_events_det / evf_encode_window_det and every
-# iwe_splat through evf_iwe_splat_det (exact, order-independent sums) instead of the float atomics.  A switch of this
-# module, not of the library: the C ABI has one entry point per form.
+# iwe_splat through evf_iwe_splat_det (exact, order-independent sums) instead of the float atomics; the spiking cells of the
+# general path through evf_neuron_bwd_det and the two-launch optimizer step through evf_clip_adam_step_det (fixed-order sums).
+# A switch of this module, not of the library: the C ABI has one entry point per form.
 _deterministic = os.environ.get("EVF_DETERMINISTIC", "0") == "1"
 
 
 def set_deterministic(on):
-    """Route the contrast-maximisation loss, the voxel binning and the IWE splats through their deterministic entry points
-    (True) or the default ones (False)."""
+    """Route the contrast-maximisation loss, the voxel binning, the IWE splats, the neuron backward of the general path's
+    spiking cells (its per-channel parameter gradients and g_P) and the two-launch clip + Adam step through their deterministic
+    entry points (True) or the default ones (False).  A cell records the switch in its forward; its backward follows that.
+    Not covered: norm_input, events_to_image(accumulate=True) with arbitrary values, the materialising interpolate, k_head_wgrad
+    for voxel inputs on the fused engine, and the non-spiking zoo on the general path (bias-gradient atomics of k_wgrad9_b3 /
+    k_wgrad9 / wg_launch, the generic-kernel-size weight-gradient atomics, k_chan_reduce, k_leaky_bwd)."""
     global _deterministic
     _deterministic = bool(on)
 

@@ -2385,3 +2385,81 @@ int evf_clip_adam_step_impl(float* param, float* grad, float* m, float* v, int64
                      (float)((double)lr / bc1), (float)sqrt(bc2), eps, norm_ws, device_step, zero_grad);
   return evf_status();
 }
+
+// ---- evf_clip_adam_step_det: the two launches above with the squared norm summed in a fixed order -------------------------
+// k_sumsq_det stores its block's sum as part[blockIdx.x] (no atomic, no word to clear); every block of k_clip_adam_det adds
+// part[0 .. npart) itself, all in the same order, so all form the same coefficient.  The grid is a function of n alone.
+static int ca_det_blocks(int64_t n) { return (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024); }
+
+__global__ void k_sumsq_det(const float* __restrict__ g, long n, float* __restrict__ part, float* __restrict__ ws, int device_step) {
+  __shared__ float red[16];
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  const long gt = (long)blockIdx.x * blockDim.x + threadIdx.x, gs = (long)gridDim.x * blockDim.x;
+  if ((((uintptr_t)g) & 15) == 0) {
+    const long n4 = n >> 2;
+    const float4* g4 = (const float4*)g;
+    for (long i = gt; i < n4; i += gs) {
+      const float4 a = g4[i];
+      s0 += a.x * a.x, s1 += a.y * a.y, s2 += a.z * a.z, s3 += a.w * a.w;
+    }
+    for (long j = (n4 << 2) + gt; j < n; j += gs) s0 += g[j] * g[j];
+  } else {
+    for (long i = gt; i < n; i += gs) s0 += g[i] * g[i];
+  }
+  const float s = evf_block_sum((s0 + s1) + (s2 + s3), red);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = s;
+    if (device_step && blockIdx.x == 0) ws[1] += 1.0f;  // single writer
+  }
+}
+
+// k_clip_adam with the norm taken from the partial sums (256 threads: thread t adds part[t], part[t + 256], ... in that order,
+// then the block's fixed tree); block 0 publishes it as ws[0]
+__global__ void k_clip_adam_det(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
+                                float max_norm, float lr, float b1, float b2, float host_step_size, float host_bc2_sqrt, float eps,
+                                const float* __restrict__ part, int npart, float* __restrict__ ws, int device_step, int zero_grad) {
+  __shared__ float red[16];
+  float a = 0.f;
+  for (int i = threadIdx.x; i < npart; i += blockDim.x) a += part[i];
+  const float total = evf_block_sum_all(a, red);
+  if (blockIdx.x == 0 && threadIdx.x == 0) ws[0] = total;
+  float coef = 1.f;
+  if (max_norm > 0.f) coef = fminf(1.f, max_norm / (sqrtf(total) + 1e-6f));
+  float step_size = host_step_size, bc2_sqrt = host_bc2_sqrt;
+  if (device_step) {  // bias corrections from the device-side counter (advanced by k_sumsq_det), in double as in k_clip_adam
+    const double t = (double)ws[1];
+    step_size = (float)((double)lr / (1.0 - pow((double)b1, t)));
+    bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, t));
+  }
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float gi = g[i] * coef;
+    const float mi = b1 * m[i] + (1.f - b1) * gi;
+    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    p[i] = p[i] - step_size * (mi / denom);
+    if (zero_grad) g[i] = 0.f;
+  }
+}
+
+extern "C" int64_t evf_clip_adam_det_ws(int64_t n) { return n > 0 ? ca_det_blocks(n) : 0; }
+
+extern "C" int evf_clip_adam_step_det(float* param, float* grad, float* m, float* v, int64_t n, float max_norm, float lr,
+                                      float beta1, float beta2, float eps, int step, float* norm_ws, int zero_grad, float* part,
+                                      int64_t part_floats, void* stream) {
+  if (!param || !grad || !m || !v || !norm_ws || n <= 0) return EVF_EINVAL;
+  const int nblk = ca_det_blocks(n);
+  if (!part || part_floats < nblk) return EVF_EINVAL;
+  hipStream_t st = EVF_STREAM(stream);
+  const int device_step = step <= 0;  // step <= 0: use (and advance) the counter in norm_ws[1]
+  hipLaunchKernelGGL(k_sumsq_det, dim3(nblk), dim3(256), 0, st, grad, (long)n, part, norm_ws, device_step);
+  double bc1 = 1.0, bc2 = 1.0;
+  if (!device_step) {
+    bc1 = 1.0 - pow((double)beta1, (double)step);
+    bc2 = 1.0 - pow((double)beta2, (double)step);
+  }
+  hipLaunchKernelGGL(k_clip_adam_det, dim3(nblk), dim3(256), 0, st, param, grad, m, v, (long)n, max_norm, lr, beta1, beta2,
+                     (float)((double)lr / bc1), (float)sqrt(bc2), eps, part, nblk, norm_ws, device_step, zero_grad);
+  return evf_status();
+}

@@ -233,8 +233,39 @@ extern "C" int evf_neuron_fwd(int kind, const float* cur, const float* v_prev, c
 // wave (a block holds (256 / Q) * Q threads, waves straddle pixels), so neither shuffle reduction applies -- g_P goes through the
 // global atomics of the Q > 64 arm (zeroed by the host wrapper) and every thread adds its channel sums into LDS itself.  A
 // variant of its own: the other instantiations compile exactly as before.
+// DET (evf_neuron_bwd_det): the same per-element body, but every sum in a fixed order and nothing atomic -- g_P of the Q > 64 /
+// NP2 arms through ng_pixel_sum_lds, the block's channel sums through LDS slots added in index order, and the block's np * C
+// sums plain-stored as row blockIdx.x of `ws` for k_neuron_rowsum.  Dynamic LDS: [4][C] sums, [slots][4][C], [blockDim] g_P.
 #define NG_REP 32
-template <int KIND, bool GST, bool PREV, bool NP2>
+
+// Sum of `v` over the Q threads of a pixel (threads g * Q .. g * Q + Q - 1 of the block; Q > 64 or not a power of two) in a fixed
+// tree; valid in the pixel's first thread (cq == 0).  Every thread of the block calls it.  s: blockDim floats of LDS.
+__device__ __forceinline__ float ng_pixel_sum_lds(float v, float* s, int Q, int cq) {
+  const int tid = (int)threadIdx.x;
+  if ((Q & 63) == 0) {  // a pixel is Q / 64 whole waves: shuffles inside the wave, the wave sums in wave order
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+    if ((tid & 63) == 0) s[tid >> 6] = v;
+    __syncthreads();
+    float t = 0.f;
+    if (cq == 0)
+      for (int w = 0; w < (Q >> 6); ++w) t += s[(tid >> 6) + w];
+    __syncthreads();
+    return t;
+  }
+  s[tid] = v;
+  __syncthreads();
+  int o = 1;
+  while (o < Q) o <<= 1;
+  for (o >>= 1; o >= 1; o >>= 1) {  // (thread cq < o reads word cq + o >= o, which nobody writes at this level)
+    if (cq < o && cq + o < Q) s[tid] += s[tid + o];
+    __syncthreads();
+  }
+  const float t = s[tid];
+  __syncthreads();
+  return t;
+}
+
+template <int KIND, bool GST, bool PREV, bool NP2, bool DET = false>
 __global__ void k_neuron_bwd(const float4* __restrict__ g_v_out, const float4* __restrict__ g_z_out,
                              const float4* __restrict__ g_z_out2, const float4* __restrict__ g_aux_out, const float4* __restrict__ v_out,
                              const float4* __restrict__ aux_out, const float4* __restrict__ v_prev,
@@ -344,6 +375,9 @@ __global__ void k_neuron_bwd(const float4* __restrict__ g_v_out, const float4* _
         // the Q threads of a pixel are consecutive lanes of one wave
         for (int o = 1; o < tpp; o <<= 1) gPp += __shfl_xor(gPp, o, 64);
         if (ok && cq == 0) g_P[pix] = gPp;
+      } else if (DET) {
+        gPp = ng_pixel_sum_lds(gPp, s_acc + 4 * C + (NP2 ? 4 * C * ((int)blockDim.x / Q) : 0), Q, cq);
+        if (ok && cq == 0) g_P[pix] = gPp;  // (a pixel's threads share one trip of one block: `ok` is theirs alike)
       } else if (ok) {
         evf_atomic_add(g_P + pix, gPp);  // g_P zeroed by the host wrapper
       }
@@ -383,6 +417,32 @@ __global__ void k_neuron_bwd(const float4* __restrict__ g_v_out, const float4* _
       }
       __syncthreads();
     }
+  } else if (DET) {
+    // one slot of [4][C] per wave (lanes below Q hold the wave's sums) or, NP2, per group of Q threads; added in slot order
+    float* slot = s_acc + 4 * C;
+    const int nslot = NP2 ? (int)blockDim.x / Q : ((int)blockDim.x + 63) >> 6;
+    if (NP2 || (int)(threadIdx.x & 63) < Q) {
+      float* mine = slot + 4 * C * (NP2 ? (int)threadIdx.x / Q : (int)threadIdx.x >> 6);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int c = 4 * cq + k;
+        mine[0 * C + c] = s0[k] * lam[k] * (1.0f - lam[k]);
+        mine[1 * C + c] = s1[k] * m1[k];
+        if (KIND == EVF_PLIF) {
+          mine[2 * C + c] = s2[k] * a2[k] * (1.0f - a2[k]);
+          mine[3 * C + c] = s3[k] * a3[k] * (1.0f - a3[k]);
+        } else if (KIND != EVF_LIF) {
+          mine[2 * C + c] = s2[k] * m2[k];
+          mine[3 * C + c] = s3[k] * a3[k] * (1.0f - a3[k]);
+        }
+      }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < (KIND == EVF_LIF ? 2 : 4) * C; i += blockDim.x) {
+      float t = 0.f;
+      for (int g = 0; g < nslot; ++g) t += slot[4 * C * g + i];
+      s_acc[i] = t;
+    }
   } else if (NP2 || (int)(threadIdx.x & 63) < Q) {  // (NP2: no meeting above, every thread adds)
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -400,6 +460,11 @@ __global__ void k_neuron_bwd(const float4* __restrict__ g_v_out, const float4* _
   }
   __syncthreads();
   const int np = KIND == EVF_LIF ? 2 : 4;
+  if (DET) {  // row blockIdx.x of ws [gridDim][np * C]: plain stores, visible to k_neuron_rowsum by stream order
+    float* row = ws + (size_t)blockIdx.x * (size_t)(np * C);
+    for (int i = threadIdx.x; i < np * C; i += blockDim.x) row[i] = s_acc[i];
+    return;
+  }
   if (!ws) {  // (no scratch: every block adds straight into the 2..4 x C outputs -- up to 1024 atomics per address)
     for (int i = threadIdx.x; i < np * C; i += blockDim.x) {
       const int p = i / C, c = i - p * C;
@@ -507,6 +572,104 @@ extern "C" int evf_neuron_bwd(int kind, const float* g_v_out, const float* g_z_o
 #undef NG_BWD
 #undef NG_BWD__
 #undef NG_BWD_
+  return evf_status();
+}
+
+// ---- evf_neuron_bwd_det: the same backward with every sum in a fixed order (no atomics, no ticket, no memset) -------------
+// k_neuron_bwd<.., DET> leaves row b = the np * C channel sums of block b in ws [nblk][np * C]; k_neuron_rowsum adds the rows
+// onto the outputs as a launch of its own (stream order makes the rows visible; a last-block finish would need an agent-scope
+// release behind the element-wise stores, and would read up to 1024 x 4096 floats through one CU).  A column's rows are cut
+// into NG_RS_GROUPS runs of consecutive rows: each run is summed in row order by one thread, the runs in run order by the first.
+#define NG_RS_GROUPS 16
+__global__ __launch_bounds__(64 * NG_RS_GROUPS) void k_neuron_rowsum(const float* __restrict__ ws, int nrows, int ncol, int C,
+                                                                     NgParams prm) {
+  __shared__ float s_run[NG_RS_GROUPS][64];
+  const int lane = threadIdx.x & 63, run = threadIdx.x >> 6, col = blockIdx.x * 64 + lane;
+  const int per = (nrows + NG_RS_GROUPS - 1) / NG_RS_GROUPS;
+  const int r0 = run * per, r1 = r0 + per < nrows ? r0 + per : nrows;
+  float t = 0.f;
+  if (col < ncol) {
+#pragma unroll 8
+    for (int r = r0; r < r1; ++r) t += ws[(size_t)r * ncol + col];
+  }
+  s_run[run][lane] = t;
+  __syncthreads();
+  if (run || col >= ncol) return;
+  float a = 0.f;
+#pragma unroll
+  for (int g = 0; g < NG_RS_GROUPS; ++g) a += s_run[g][lane];
+  const int p = col / C, c = col - p * C;
+  if (prm.g[p]) prm.g[p][c] += a;  // single writer
+}
+
+// launch geometry of evf_neuron_bwd (block size, blocks), restated for the deterministic twin: the rows of its scratch are the blocks
+static bool ng_bwd_geometry(int64_t npix, int C, int kind, int* bs, int* nblk) {
+  if (npix <= 0 || C <= 0 || (C & 3) || C > 1024 || kind < 0 || kind > 3) return false;
+  const int Q = C >> 2;
+  *bs = ng_block(Q);
+  const long total = npix * Q;
+  long want = (total + (long)*bs * 4 - 1) / ((long)*bs * 4);
+  if (want < 64) want = (total + *bs - 1) / *bs < 64 ? (total + *bs - 1) / *bs : 64;
+  *nblk = (int)(want < 1024 ? want : 1024);
+  return true;
+}
+
+extern "C" int64_t evf_neuron_bwd_det_ws(int64_t npix, int C, int kind) {
+  int bs, nblk;
+  if (!ng_bwd_geometry(npix, C, kind, &bs, &nblk)) return 0;
+  return (int64_t)nblk * (kind == EVF_LIF ? 2 : 4) * C;
+}
+
+extern "C" int evf_neuron_bwd_det(int kind, const float* g_v_out, const float* g_z_out, const float* g_z_out2,
+                                  const float* g_aux_out, const float* v_out, const float* aux_out, const float* v_prev,
+                                  const float* z_prev, const float* aux_prev, const float* P, const float* p0, const float* p1,
+                                  const float* p2, const float* p3, int64_t npix, int C, int hard_reset, int surrogate,
+                                  float act_width, float* g_cur, float* g_v_prev, float* g_z_prev, float* g_aux_prev, float* g_P,
+                                  float* g_p0, float* g_p1, float* g_p2, float* g_p3, float* ws, int64_t ws_floats, void* stream) {
+  int bs, nblk;
+  if (!v_out || !p0 || !p1 || !g_cur || !ng_bwd_geometry(npix, C, kind, &bs, &nblk)) return EVF_EINVAL;
+  const int Q = C >> 2;
+  const bool np2 = Q < 64 && (Q & (Q - 1));
+  if (kind != EVF_LIF && (!p2 || !p3 || !aux_out || (g_v_prev && !g_aux_prev))) return EVF_EINVAL;
+  if ((kind == EVF_PLIF || kind == EVF_XLIF) && (!P || !g_P)) return EVF_EINVAL;
+  if (kind == EVF_ALIF && g_v_prev && !g_z_prev) return EVF_EINVAL;
+  const int ncol = (kind == EVF_LIF ? 2 : 4) * C;
+  if (!ws || ws_floats < (int64_t)nblk * ncol) return EVF_EINVAL;
+  hipStream_t st = EVF_STREAM(stream);
+  NgParams prm = {{p0, p1, p2, p3}, {g_p0, g_p1, g_p2, g_p3}};
+  // LDS: the [4][C] sums, below 64 quads one [4][C] slot per wave (per group of Q threads: NP2), blockDim words for g_P
+  const int nslot = Q >= 64 ? 0 : (np2 ? bs / Q : (bs + 63) >> 6);
+  const size_t smem = sizeof(float) * ((size_t)4 * C * (1 + nslot) + (size_t)bs);
+  const bool gst = g_v_out || g_z_out2 || g_aux_out, prev = v_prev || z_prev || aux_prev;
+#define NG_BWD_(K, G_, P_, N_)                                                                                                  \
+  hipLaunchKernelGGL((k_neuron_bwd<K, G_, P_, N_, true>), dim3(nblk), dim3(bs), smem, st, (const float4*)g_v_out,              \
+                     (const float4*)g_z_out, (const float4*)g_z_out2, (const float4*)g_aux_out, (const float4*)v_out,          \
+                     (const float4*)aux_out, (const float4*)v_prev, (const float4*)z_prev, (const float4*)aux_prev, P, prm,    \
+                     (long)npix, C, hard_reset, surrogate, act_width, (float4*)g_cur, (float4*)g_v_prev, (float4*)g_z_prev,    \
+                     (float4*)g_aux_prev, g_P, ws)
+#define NG_BWD__(K, N_)                               \
+  do {                                                \
+    if (gst && prev) NG_BWD_(K, true, true, N_);      \
+    else if (gst) NG_BWD_(K, true, false, N_);        \
+    else if (prev) NG_BWD_(K, false, true, N_);       \
+    else NG_BWD_(K, false, false, N_);                \
+  } while (0)
+#define NG_BWD(K)               \
+  do {                          \
+    if (np2) NG_BWD__(K, true); \
+    else NG_BWD__(K, false);    \
+  } while (0)
+  switch (kind) {
+    case EVF_LIF: NG_BWD(EVF_LIF); break;
+    case EVF_PLIF: NG_BWD(EVF_PLIF); break;
+    case EVF_ALIF: NG_BWD(EVF_ALIF); break;
+    default: NG_BWD(EVF_XLIF); break;
+  }
+#undef NG_BWD
+#undef NG_BWD__
+#undef NG_BWD_
+  if (g_p0 || g_p1 || g_p2 || g_p3)
+    hipLaunchKernelGGL(k_neuron_rowsum, dim3(evf_cdiv(ncol, 64)), dim3(64 * NG_RS_GROUPS), 0, st, ws, nblk, ncol, C, prm);
   return evf_status();
 }
 

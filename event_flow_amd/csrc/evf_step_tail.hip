@@ -253,3 +253,8 @@ extern "C" int evf_clip_adam_fused(float* param, float* grad, float* m, float* v
                      beta1, beta2, (float)((double)lr / bc1), (float)sqrt(bc2), eps, ws, device_step, zero_grad);
   return evf_status();
 }
+
+// 1: evf_clip_adam_fused(n, grad) runs the single launch above (whose norm is reproducible as it stands); 0: the two-launch form
+extern "C" int evf_clip_adam_fused_fits(int64_t n, const float* grad) {
+  return n > 0 && n <= CA_MAX_N && !((uintptr_t)grad & 15);
+}

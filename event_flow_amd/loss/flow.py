@@ -17,7 +17,8 @@ Differences in mechanism, not in results:
     The same switch routes every `iwe_splat` (the images of `FWL`, `RSAT`, `compute_window_*`, `compute_pol_iwe`,
     `deblur_events`) through `evf_iwe_splat_det` and voxel grids through `evf_encode_events_det` /
     `evf_encode_window_det`: the fixed-point stripes of the loss, with k from `splat_det_bits`.  A shape
-    those refuse raises `EvflowError`; nothing falls back to the atomics.
+    those refuse raises `EvflowError`; nothing falls back to the atomics.  It also routes the neuron backward of the general
+    path's spiking cells (`evf_neuron_bwd_det`) and the two-launch optimizer step (`evf_clip_adam_step_det`): fixed-order sums.
 """
 
 import math

@@ -384,6 +384,23 @@ def _neuron_ws(dev):
     return _NEURON_WS[dev]
 
 
+# evf_neuron_bwd_det_ws at its worst case (1024 blocks x 4 parameter rows x 1024 channels: 16 MiB), so that ONE buffer per device
+# serves every cell and is never reallocated: captured graphs hold its address
+NEURON_DET_WS_FLOATS = 1024 * 4 * 1024
+_NEURON_DET_WS = {}
+
+
+def _neuron_det_ws(dev):
+    """Scratch of evf_neuron_bwd_det (the blocks' channel sums, one row per block; need not be zero).  One per device, calls are
+    stream-ordered.  Allocated outside any capture: a tensor made inside one belongs to the capture's memory pool."""
+    if dev not in _NEURON_DET_WS:
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.EvflowError("the deterministic neuron backward allocates its scratch on first use, which must not be inside "
+                                   "a capture: run the step eagerly once first")
+        _NEURON_DET_WS[dev] = torch.empty(NEURON_DET_WS_FLOATS, dtype=torch.float32, device=dev)
+    return _NEURON_DET_WS[dev]
+
+
 # State routing (train.capture_window_cycle): a step replayed from hipGraphs needs its recurrent state at FIXED addresses, and the
 # last graph of a cycle has to leave its final state where the first graph reads it.  Instead of copying (410 MB of state per
 # step of the LIF-EV-FlowNet of BASELINE configs[3]: 0.25 ms, and memcpy NODES in the graph) a cell whose PREVIOUS state starts
@@ -540,6 +557,7 @@ class _CellStep(torch.autograd.Function):
                   B * Ho * Wo, C, 1 if cell.hard_reset else 0, _lib.ptr(new[0]), _lib.ptr(new[1]),
                   _lib.ptr(new[2]) if ns == 3 else None, out_ptr)
         ctx.cell, ctx.kind, ctx.ns = cell, kind, ns
+        ctx.det = _lib.deterministic()  # the backward follows the switch as it stood HERE: a toggle in between cannot mix paths
         tag = spike_tag(x)
         ctx.exact_from = tag[1] if tag is not None else None  # provenance of the input (conv_wgrad)
         ctx.geom = (B, H, W, Cin, Ho, Wo, C, k, s)
@@ -595,7 +613,9 @@ class _CellStep(torch.autograd.Function):
         g_prm = [d_prm[i].view(-1) if d_prm[i] is not None else
                  (_lib.zeros(C, dtype=torch.float32, device=dev) if (prm[i] is not None and need[6 + i]) else None)
                  for i in range(4)]
-        _lib.call("evf_neuron_bwd", kind, _lib.ptr(gs[0]) if gs is not None else None, _lib.ptr(gon),
+        # deterministic mode: the fixed-order twin, its scratch followed by the size
+        ws = (_lib.ptr(_neuron_det_ws(dev)), NEURON_DET_WS_FLOATS) if ctx.det else (_lib.ptr(_neuron_ws(dev)),)
+        _lib.call("evf_neuron_bwd_det" if ctx.det else "evf_neuron_bwd", kind, _lib.ptr(gs[0]) if gs is not None else None, _lib.ptr(gon),
                   _lib.ptr(gs[1]) if gs is not None else _lib.ptr(gon2), _lib.ptr(gs[2]) if (gs is not None and ns == 3) else None,
                   _lib.ptr(new[0]), _lib.ptr(new[2]) if ns == 3 else None, _lib.ptr(sp[0]) if sp is not None else None,
                   _lib.ptr(sp[1]) if sp is not None else None, _lib.ptr(sp[2]) if (sp is not None and ns == 3) else None,
@@ -603,7 +623,7 @@ class _CellStep(torch.autograd.Function):
                   1 if cell.hard_reset else 0, SURROGATE_ID[cell.activation], act_width(cell), _lib.ptr(g_cur),
                   _lib.ptr(g_prev[0]) if want_prev else None, _lib.ptr(g_prev[1]) if want_prev else None,
                   _lib.ptr(g_prev[2]) if (want_prev and ns == 3) else None, _lib.ptr(g_P),
-                  _lib.ptr(g_prm[0]), _lib.ptr(g_prm[1]), _lib.ptr(g_prm[2]), _lib.ptr(g_prm[3]), _lib.ptr(_neuron_ws(dev)))
+                  _lib.ptr(g_prm[0]), _lib.ptr(g_prm[1]), _lib.ptr(g_prm[2]), _lib.ptr(g_prm[3]), *ws)
         g_wff = g_wrec = g_x = None
         if need[4]:
             d = bound_grad(wff)

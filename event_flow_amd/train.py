@@ -41,6 +41,8 @@ class FlatAdam:
         self.v = torch.zeros(n, dtype=torch.float32, device=dev)
         # [0] squared gradient norm of the last step, [1] device-side step counter, [2..4] the fused kernel's running sum / tickets
         self.norm_ws = torch.zeros(8, dtype=torch.float32, device=dev)
+        # deterministic mode, two-launch step: one partial sum of squares per block (<= 4 KiB; need not be zero)
+        self.norm_part = torch.empty(int(_lib.load().evf_clip_adam_det_ws(n)), dtype=torch.float32, device=dev)
         off = 0
         for p in self.params:
             k = p.numel()
@@ -103,10 +105,15 @@ class FlatAdam:
     def step(self):
         self.steps += 1
         # one launch (squared norm, grid hand-shake, clip + Adam + zero_grad; csrc/evf_step_tail.hip); EVF_FUSED_ADAM=0: fill + two
-        _lib.call("evf_clip_adam_fused" if FUSED_ADAM else "evf_clip_adam_step", _lib.ptr(self.flat_param), _lib.ptr(self.flat_grad), _lib.ptr(self.m),
+        # deterministic mode: the single launch sums in a fixed order as it stands; where the call would reach the two-launch form
+        # (its norm a float atomic per block) the twin with per-block partial sums takes over
+        name, part = ("evf_clip_adam_fused" if FUSED_ADAM else "evf_clip_adam_step"), ()
+        if _lib.deterministic() and not (FUSED_ADAM and _lib.load().evf_clip_adam_fused_fits(self.n, _lib.ptr(self.flat_grad))):
+            name, part = "evf_clip_adam_step_det", (_lib.ptr(self.norm_part), self.norm_part.numel())
+        _lib.call(name, _lib.ptr(self.flat_param), _lib.ptr(self.flat_grad), _lib.ptr(self.m),
                   _lib.ptr(self.v), self.n, float(self.clip) if self.clip is not None else 0.0, float(self.lr),
                   float(self.betas[0]), float(self.betas[1]), float(self.eps), 0 if self.device_step else self.steps,
-                  _lib.ptr(self.norm_ws), 1)
+                  _lib.ptr(self.norm_ws), 1, *part)
         self._grad_clean = True
         # the kernel rewrote the parameters behind torch's version counters: drop the
         # engine's packed-weight cache explicitly

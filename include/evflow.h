@@ -806,6 +806,22 @@ int evf_neuron_bwd(int kind, const float* g_v_out, const float* g_z_out, const f
                    int surrogate, float act_width, float* g_cur, float* g_v_prev, float* g_z_prev,
                    float* g_aux_prev, float* g_P, float* g_p0, float* g_p1, float* g_p2, float* g_p3,
                    float* ws, void* stream);
+/* The deterministic form of evf_neuron_bwd: the same arguments, `ws` followed by its size in floats.  g_cur / g_v_prev /
+ * g_z_prev / g_aux_prev are bit-identical to evf_neuron_bwd's; g_P and the parameter gradients (+= onto their contents, single
+ * writer, null = skip) are functions of the arguments alone -- no atomics: a block adds its channel sums in LDS in index order
+ * and stores them as row blockIdx of ws [blocks][np * C] (np = 2 for LIF, 4 otherwise); a second launch adds the rows in row
+ * order (16 runs of consecutive rows per column, then the runs in run order) onto the outputs.  Launch geometry as
+ * evf_neuron_bwd.  ws: mandatory, >= evf_neuron_bwd_det_ws(npix, C, kind) floats (0 for arguments the call refuses; at most
+ * 1024 * 4 * 1024), need NOT be zero, contents unspecified afterwards; it holds no ticket.  No memset of g_P.  EVF_EINVAL
+ * for everything evf_neuron_bwd refuses and for a null or short ws, before anything is launched. */
+int64_t evf_neuron_bwd_det_ws(int64_t npix, int C, int kind);
+int evf_neuron_bwd_det(int kind, const float* g_v_out, const float* g_z_out, const float* g_z_out2,
+                       const float* g_aux_out, const float* v_out, const float* aux_out, const float* v_prev,
+                       const float* z_prev, const float* aux_prev, const float* P, const float* p0,
+                       const float* p1, const float* p2, const float* p3, int64_t npix, int C, int hard_reset,
+                       int surrogate, float act_width, float* g_cur, float* g_v_prev, float* g_z_prev,
+                       float* g_aux_prev, float* g_P, float* g_p0, float* g_p1, float* g_p2, float* g_p3,
+                       float* ws, int64_t ws_floats, void* stream);
 /* P [B,Ho,Wo] = avg_pool2d(mean_c |x|, k, stride, k/2) (spiking_submodules.py:212,418);
  * absmean_ws [B*H*W] workspace.  Backward adds/writes sign(x)/C * pool^T(g_P) into g_x. */
 int evf_pretrace_fwd(const float* x, int ldx, int B, int H, int W, int C, int ksz, int stride,
@@ -901,6 +917,17 @@ int evf_clip_adam_step(float* param, float* grad, float* m, float* v, int64_t n,
 int evf_clip_adam_fused(float* param, float* grad, float* m, float* v, int64_t n,
                         float max_norm, float lr, float beta1, float beta2, float eps, int step,
                         float* ws, int zero_grad, void* stream);
+/* 1 when evf_clip_adam_fused(n, grad) runs its single-launch form, 0 when it hands over to the two launches of
+ * evf_clip_adam_step (n above 2^20, or a gradient pointer that is not 16-byte aligned). */
+int evf_clip_adam_fused_fits(int64_t n, const float* grad);
+/* evf_clip_adam_step with a reproducible norm: the first launch stores one partial sum of squares per block in
+ * part [>= evf_clip_adam_det_ws(n) floats, <= 1024; need not be zero], every block of the second adds them in the same fixed
+ * order -- no atomic, no memset; the grid is a function of n alone.  norm_ws[0], norm_ws[1], step and zero_grad as in
+ * evf_clip_adam_step; any n >= 1, any alignment of grad.  EVF_EINVAL for a null or short part. */
+int64_t evf_clip_adam_det_ws(int64_t n);
+int evf_clip_adam_step_det(float* param, float* grad, float* m, float* v, int64_t n,
+                           float max_norm, float lr, float beta1, float beta2, float eps, int step,
+                           float* norm_ws, int zero_grad, float* part, int64_t part_floats, void* stream);
 /* Every partial sum a window's backward leaves behind, added to the (flat) parameter gradients in one launch
  * (evf_reduce_slabs_multi + evf_sum_rows x 2 + evf_add_segments; train_flow.py:154 loss.backward()'s parameter gradients):
  *   slabs[t] [nslab][9*32*32] partial sums of conv weight t (nslabs <= 16) -> slab_dst[t] [32][32][3][3] +=;
