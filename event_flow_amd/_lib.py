@@ -155,6 +155,9 @@ NETWORK_SIGNATURES = {
     "evf_wgrad_teams_select": [I],
     "evf_conv2d_wgrad_ws": [I, I, I, I, I, I, I],
     "evf_conv2d_wgrad": [P, I, P, I, P, P, I, I, I, I, I, I, I, I, I, I, P, P],
+    # the deterministic form: evf_conv2d_wgrad's arguments (g_bias must be null), ws followed by its size in floats
+    "evf_conv2d_wgrad_det_ws": [I, I, I, I, I, I, I],
+    "evf_conv2d_wgrad_det": [P, I, P, I, P, P, I, I, I, I, I, I, I, I, I, I, P, L, P],
     "evf_neuron_fwd": [I, P, P, P, P, P, P, P, P, P, P, L, I, I, P, P, P, P, P],
     "evf_conv2d_fwd_b3_parts": [P, I, P, P, I, I, I, I, I, I, I, I, I, P, L, P, P],
     "evf_lif_fwd_parts": [P, I, L, P, I, L, P, P, P, P, P, L, I, I, P, P, P, P],
@@ -175,6 +178,9 @@ NETWORK_SIGNATURES = {
     "evf_upsample_nearest_bwd": [P, L, I, I, I, P, P],
     "evf_apply_pixel_mask": [P, P, I, I, I, I, P],
     "evf_chan_reduce": [P, I, P, I, P, P, I, I, L, I, P, P],
+    # the deterministic form: evf_chan_reduce's arguments, accumulate, ws and its size in floats
+    "evf_chan_reduce_det_ws": [I, L, I],
+    "evf_chan_reduce_det": [P, I, P, I, P, P, I, I, L, I, P, I, P, L, P],
     "evf_chan_affine": [P, I, P, I, P, P, P, I, L, I, P, I, P],
     "evf_act_fwd": [I, P, P, L, P, P],
     "evf_act_bwd": [I, P, P, L, P, P],
@@ -182,6 +188,9 @@ NETWORK_SIGNATURES = {
     "evf_lstm_fwd": [P, P, L, I, P, P, P],
     "evf_lstm_bwd": [P, P, P, P, P, L, I, P, P, P],
     "evf_leaky_bwd": [P, P, P, P, P, I, L, I, P, P, P, P],
+    # the deterministic form: evf_leaky_bwd's arguments, ws and its size in floats
+    "evf_leaky_bwd_det_ws": [L, I],
+    "evf_leaky_bwd_det": [P, P, P, P, P, I, L, I, P, P, P, P, L, P],
     "evf_spike_fwd": [P, P, I, L, P, P],
     "evf_spike_bwd": [I, P, P, I, P, F, L, P, P],
     "evf_gru_gates_fwd": [P, P, P, L, P, P, P, P],
@@ -190,7 +199,8 @@ NETWORK_SIGNATURES = {
     "evf_gru_gates_bwd": [P, P, P, L, P, P, P],
 }
 RESTYPES = {"evf_head1x1_ws": ctypes.c_int64, "evf_comm_last_error": ctypes.c_char_p, "evf_conv2d_packed_size": ctypes.c_int64, "evf_conv2d_b3_packed_size": ctypes.c_int64, "evf_conv2d_b3_ws": ctypes.c_int64, "evf_conv2d_wgrad_ws": ctypes.c_int64, "evf_cm_loss_ws": ctypes.c_int64, "evf_cm_loss_ws_det": ctypes.c_int64, "evf_cm_loss_bwd_ws_det": ctypes.c_int64,
-            "evf_neuron_bwd_det_ws": ctypes.c_int64, "evf_clip_adam_det_ws": ctypes.c_int64}
+            "evf_neuron_bwd_det_ws": ctypes.c_int64, "evf_clip_adam_det_ws": ctypes.c_int64,
+            "evf_chan_reduce_det_ws": ctypes.c_int64, "evf_leaky_bwd_det_ws": ctypes.c_int64, "evf_conv2d_wgrad_det_ws": ctypes.c_int64}
 SIGNATURES.update(NETWORK_SIGNATURES)
 
 _lib = None
@@ -198,7 +208,8 @@ _lib = None
 # Deterministic mode (EVF_DETERMINISTIC=1 at import, set_deterministic): the contrast-maximisation loss goes through
 # evf_cm_loss_fwd_det / evf_cm_loss_bwd_det, voxel grids through evf_encode_events_det / evf_encode_window_det and every
 # iwe_splat through evf_iwe_splat_det (exact, order-independent sums) instead of the float atomics; the spiking cells of the
-# general path through evf_neuron_bwd_det and the two-launch optimizer step through evf_clip_adam_step_det (fixed-order sums).
+# general path through evf_neuron_bwd_det and the two-launch optimizer step through evf_clip_adam_step_det (fixed-order sums);
+# the non-spiking layers through evf_conv2d_wgrad_det, evf_chan_reduce_det and evf_leaky_bwd_det.
 # A switch of this module, not of the library: the C ABI has one entry point per form.
 _deterministic = os.environ.get("EVF_DETERMINISTIC", "0") == "1"
 
@@ -207,9 +218,11 @@ def set_deterministic(on):
     """Route the contrast-maximisation loss, the voxel binning, the IWE splats, the neuron backward of the general path's
     spiking cells (its per-channel parameter gradients and g_P) and the two-launch clip + Adam step through their deterministic
     entry points (True) or the default ones (False).  A cell records the switch in its forward; its backward follows that.
+    The non-spiking layers of the general path follow the same rule: every weight gradient through evf_conv2d_wgrad_det, every
+    bias gradient and every statistic of batch / instance / group norm through evf_chan_reduce_det, the leaky cells' g_leak through
+    evf_leaky_bwd_det (fixed-order sums).
     Not covered: norm_input, events_to_image(accumulate=True) with arbitrary values, the materialising interpolate, k_head_wgrad
-    for voxel inputs on the fused engine, and the non-spiking zoo on the general path (bias-gradient atomics of k_wgrad9_b3 /
-    k_wgrad9 / wg_launch, the generic-kernel-size weight-gradient atomics, k_chan_reduce, k_leaky_bwd)."""
+    for voxel inputs on the fused engine."""
     global _deterministic
     _deterministic = bool(on)
 
@@ -301,6 +314,7 @@ _PROF_VARIANT = {
     "evf_conv2d_fwd_b3_parts": lambda a: ",".join(str(int(v)) for v in a[5:12]),
     "evf_conv2d_dgrad_b3": lambda a: ",".join(str(int(v)) for v in a[5:12]),
     "evf_conv2d_wgrad": lambda a: ",".join(str(int(v)) for v in a[6:13]),
+    "evf_conv2d_wgrad_det": lambda a: ",".join(str(int(v)) for v in a[6:13]),
 }
 
 

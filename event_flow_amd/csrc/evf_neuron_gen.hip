@@ -731,6 +731,11 @@ extern "C" int evf_leaky_fwd(const float* cur, const float* prev, const float* r
 // g_leak[c] += sum g_mix (prev - cur) lam (1 - lam), with cur recovered from mix as (mix - prev lam) / (1 - lam)
 __device__ float g_leaky_rep[NG_REP * 1024];  // zero at load, zero after every evf_leaky_bwd
 
+// DET (evf_leaky_bwd_det): the same per-element body, block size, grid and trips (g_cur / g_prev: the default's bits), the sum in
+// a fixed order and nothing atomic; `g_leak` is then the scratch [gridDim][C] whose row blockIdx.x takes the block's C sums for
+// k_neuron_rowsum, and g_leaky_rep is not touched.  The in-block part is the twin of k_neuron_bwd<.., DET>'s (a second copy: sharing
+// it would change what that kernel's instantiations compile to).  Dynamic LDS: [C] sums, below 64 quads [slots][C] behind them.
+template <bool DET = false>
 __global__ void k_leaky_bwd(const float4* __restrict__ g_out, const float4* __restrict__ g_state, const float4* __restrict__ mix,
                             const float4* __restrict__ prev, const float* __restrict__ leak, int act, long npix, int C,
                             float4* __restrict__ g_cur, float4* __restrict__ g_prev, float* __restrict__ g_leak) {
@@ -761,7 +766,46 @@ __global__ void k_leaky_bwd(const float4* __restrict__ g_out, const float4* __re
     g_cur[e] = make_float4(gc[0], gc[1], gc[2], gc[3]);
     if (g_prev) g_prev[e] = make_float4(gp[0], gp[1], gp[2], gp[3]);
   }
-  if (g_leak) {
+  if (DET) {
+    if (!g_leak) return;  // (uniform)
+    const bool np2 = Q < 64 && (Q & (Q - 1));
+    if (Q >= 64) {
+      // blockDim / Q threads own a channel quad (threads t, t + Q, ...): they add in turns with plain LDS read-modify-writes
+      const int turns = (int)blockDim.x / Q, mine = (int)threadIdx.x / Q;
+      for (int t = 0; t < turns; ++t) {
+        if (t == mine) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) s_acc[4 * cq + k] += s0[k] * lam[k] * (1.0f - lam[k]);
+        }
+        __syncthreads();
+      }
+    } else {
+      // Q a power of two: lanes l, l + Q, ... of a wave own the same channels and meet in registers, lanes below Q hold the wave's
+      // sums; one slot of [C] per wave or, Q no power of two, per group of Q threads; thread i adds word i in slot order
+      if (!np2) {
+        for (int o = Q; o < 64; o <<= 1) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) s0[k] += __shfl_xor(s0[k], o, 64);
+        }
+      }
+      float* slot = s_acc + C;
+      const int nslot = np2 ? (int)blockDim.x / Q : ((int)blockDim.x + 63) >> 6;
+      if (np2 || (int)(threadIdx.x & 63) < Q) {
+        float* mine = slot + C * (np2 ? (int)threadIdx.x / Q : (int)threadIdx.x >> 6);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mine[4 * cq + k] = s0[k] * lam[k] * (1.0f - lam[k]);
+      }
+      __syncthreads();
+      for (int i = threadIdx.x; i < C; i += blockDim.x) {
+        float t = 0.f;
+        for (int g = 0; g < nslot; ++g) t += slot[C * g + i];
+        s_acc[i] = t;
+      }
+      __syncthreads();
+    }
+    float* row = g_leak + (size_t)blockIdx.x * (size_t)C;  // plain stores, visible to k_neuron_rowsum by stream order
+    for (int i = threadIdx.x; i < C; i += blockDim.x) row[i] = s_acc[i];
+  } else if (g_leak) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) atomicAdd(&s_acc[4 * cq + k], s0[k] * lam[k] * (1.0f - lam[k]));
     __syncthreads();
@@ -789,12 +833,51 @@ extern "C" int evf_leaky_bwd(const float* g_out, const float* g_state, const flo
   const int Q = C >> 2, bs = ng_block(Q);
   const long total = npix * Q;
   const int nblk = (int)((total + bs - 1) / bs < 1024 ? (total + bs - 1) / bs : 1024);
-  hipLaunchKernelGGL(k_leaky_bwd, dim3(nblk), dim3(bs), sizeof(float) * (size_t)C, EVF_STREAM(stream), (const float4*)g_out,
+  hipLaunchKernelGGL(k_leaky_bwd<>, dim3(nblk), dim3(bs), sizeof(float) * (size_t)C, EVF_STREAM(stream), (const float4*)g_out,
                      (const float4*)g_state, (const float4*)mix, (const float4*)prev, leak, act, (long)npix, C,
                      (float4*)g_cur, (float4*)g_prev, g_leak);
   if (g_leak)
     hipLaunchKernelGGL(k_leaky_finish, dim3(evf_cdiv(C, 64)), dim3(64), 0, EVF_STREAM(stream), nblk < NG_REP ? nblk : NG_REP, C,
                        g_leak);
+  return evf_status();
+}
+
+// ---- evf_leaky_bwd_det: the same backward with g_leak summed in a fixed order (no atomics, no replicas, no memset) -----------
+// launch geometry of evf_leaky_bwd, restated: the rows of the scratch are the blocks
+static bool leaky_bwd_geometry(int64_t npix, int C, int* bs, int* nblk) {
+  if (npix <= 0 || C <= 0 || (C & 3) || C > 1024) return false;
+  const int Q = C >> 2;
+  *bs = ng_block(Q);
+  const long total = npix * Q;
+  *nblk = (int)((total + *bs - 1) / *bs < 1024 ? (total + *bs - 1) / *bs : 1024);
+  return true;
+}
+
+extern "C" int64_t evf_leaky_bwd_det_ws(int64_t npix, int C) {
+  int bs, nblk;
+  if (!leaky_bwd_geometry(npix, C, &bs, &nblk)) return 0;
+  return (int64_t)nblk * C;
+}
+
+extern "C" int evf_leaky_bwd_det(const float* g_out, const float* g_state, const float* mix, const float* prev, const float* leak,
+                                 int act, int64_t npix, int C, float* g_cur, float* g_prev, float* g_leak, float* ws,
+                                 int64_t ws_floats, void* stream) {
+  int bs, nblk;
+  if (!mix || !leak || !g_cur || (!g_out && !g_state) || !leaky_bwd_geometry(npix, C, &bs, &nblk) || act < 0 || act > 3)
+    return EVF_EINVAL;
+  if (!ws || ws_floats < (int64_t)nblk * C) return EVF_EINVAL;
+  const int Q = C >> 2;
+  const bool np2 = Q < 64 && (Q & (Q - 1));
+  // LDS: the [C] sums, below 64 quads one [C] slot per wave (per group of Q threads when Q is no power of two)
+  const int nslot = Q >= 64 ? 0 : (np2 ? bs / Q : (bs + 63) >> 6);
+  hipStream_t st = EVF_STREAM(stream);
+  hipLaunchKernelGGL(k_leaky_bwd<true>, dim3(nblk), dim3(bs), sizeof(float) * (size_t)C * (1 + nslot), st, (const float4*)g_out,
+                     (const float4*)g_state, (const float4*)mix, (const float4*)prev, leak, act, (long)npix, C, (float4*)g_cur,
+                     (float4*)g_prev, g_leak ? ws : nullptr);
+  if (g_leak) {
+    NgParams prm = {{nullptr, nullptr, nullptr, nullptr}, {g_leak, nullptr, nullptr, nullptr}};
+    hipLaunchKernelGGL(k_neuron_rowsum, dim3(evf_cdiv(C, 64)), dim3(64 * NG_RS_GROUPS), 0, st, ws, nblk, C, C, prm);
+  }
   return evf_status();
 }
 

@@ -13,6 +13,10 @@
 //   mode 2:  y * (x - center) * scale          (y = upstream gradient: sum g * xhat)
 // `out` must be zeroed by the caller.  Block = 256 threads = (256 / CT) pixel lanes x CT channel lanes, CT = min(C, 64)
 // rounded to a power of two; a block walks `ppb` pixels of ONE group.
+// DET (evf_chan_reduce_det): the in-block part is ordered as it stands (a strided loop per thread, then one thread adds the pixel
+// lanes in lane order); instead of the atomic, block b of group g plain-stores its C sums as row b of out = ws [G][blocks per
+// group][C] for k_chan_rowsum.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void k_chan_reduce(const float* __restrict__ x, const float* __restrict__ y,
                                                      const float* __restrict__ center, const float* __restrict__ scale, int mode,
                                                      int G, long npg, int C, int ldx, int ldy, int ct, int ppb,
@@ -42,7 +46,10 @@ __global__ __launch_bounds__(256) void k_chan_reduce(const float* __restrict__ x
     if (pl == 0 && c < C) {
       float t = 0.f;
       for (int q = 0; q < npl; ++q) t += s[q * ct + cl];
-      evf_atomic_add(out + g * C + c, t);
+      if (DET)
+        out[((long)g * blocks_per_group + (long)(blockIdx.x % blocks_per_group)) * C + c] = t;
+      else
+        evf_atomic_add(out + g * C + c, t);
     }
     __syncthreads();
   }
@@ -64,8 +71,76 @@ extern "C" int evf_chan_reduce(const float* x, int ldx, const float* y, int ldy,
   if (bpg < 1) bpg = 1;
   const int ppb = (int)evf_cdiv(npg, bpg);
   bpg = evf_cdiv(npg, ppb);
-  hipLaunchKernelGGL(k_chan_reduce, dim3((unsigned)(bpg * G)), dim3(256), 0, st, x, y, center, scale, mode, G, (long)npg, C, ldx,
+  hipLaunchKernelGGL(k_chan_reduce<>, dim3((unsigned)(bpg * G)), dim3(256), 0, st, x, y, center, scale, mode, G, (long)npg, C, ldx,
                      ldy, ct, ppb, out);
+  return evf_status();
+}
+
+// ---- evf_chan_reduce_det: the same sums in a fixed order (no atomics, no memset) -----------------------------------------------
+// k_chan_reduce<DET> leaves row b = the C sums of block b of group g in ws [G][nrows][C]; k_chan_rowsum (the sibling of
+// k_neuron_rowsum for G groups and a plain output) cuts a column's rows into CR_RUNS runs of consecutive rows, adds each run in
+// row order (one thread per run) and the runs in run order, and stores the sum (accumulate 0) or adds it onto out (1): a single
+// writer per output.  Stream order makes the rows visible.
+#define CR_RUNS 16
+__global__ __launch_bounds__(64 * CR_RUNS) void k_chan_rowsum(const float* __restrict__ ws, int nrows, int C, int accumulate,
+                                                              float* __restrict__ out) {
+  __shared__ float s_run[CR_RUNS][64];
+  const int ncb = (C + 63) >> 6;  // column blocks per group
+  const int lane = threadIdx.x & 63, run = threadIdx.x >> 6, g = blockIdx.x / ncb, col = (blockIdx.x % ncb) * 64 + lane;
+  const int per = (nrows + CR_RUNS - 1) / CR_RUNS;
+  const int r0 = run * per, r1 = r0 + per < nrows ? r0 + per : nrows;
+  const float* __restrict__ p = ws + (size_t)g * nrows * C;
+  float t = 0.f;
+  if (col < C) {
+#pragma unroll 8
+    for (int r = r0; r < r1; ++r) t += p[(size_t)r * C + col];
+  }
+  s_run[run][lane] = t;
+  __syncthreads();
+  if (run || col >= C) return;
+  float a = 0.f;
+#pragma unroll
+  for (int q = 0; q < CR_RUNS; ++q) a += s_run[q][lane];
+  float* d = out + (size_t)g * C + col;
+  *d = accumulate ? *d + a : a;
+}
+
+// launch geometry of evf_chan_reduce (channel lanes, pixels per block, blocks per group), restated for the deterministic twin:
+// the rows of its scratch are the blocks of a group
+static bool chan_geometry(int G, int64_t npg, int C, int* ct, int* ppb, long* bpg) {
+  if (G <= 0 || npg <= 0 || C <= 0) return false;
+  *ct = 1;
+  while (*ct < C && *ct < 64) *ct <<= 1;
+  long b = evf_cdiv(2048, G);
+  const long maxb = evf_cdiv(npg, (long)(256 / *ct) * 8);
+  if (b > maxb) b = maxb;
+  if (b < 1) b = 1;
+  *ppb = (int)evf_cdiv(npg, b);
+  *bpg = evf_cdiv(npg, *ppb);
+  return true;
+}
+
+extern "C" int64_t evf_chan_reduce_det_ws(int G, int64_t npg, int C) {
+  int ct, ppb;
+  long bpg;
+  if (!chan_geometry(G, npg, C, &ct, &ppb, &bpg)) return 0;
+  return (int64_t)G * bpg * C;
+}
+
+extern "C" int evf_chan_reduce_det(const float* x, int ldx, const float* y, int ldy, const float* center, const float* scale,
+                                   int mode, int G, int64_t npg, int C, float* out, int accumulate, float* ws, int64_t ws_floats,
+                                   void* stream) {
+  int ct, ppb;
+  long bpg;
+  if (!x || !out || !chan_geometry(G, npg, C, &ct, &ppb, &bpg) || ldx < C || mode < 0 || mode > 2 ||
+      (mode == 2 && (!y || ldy < C)))
+    return EVF_EINVAL;
+  if (!ws || ws_floats < (int64_t)G * bpg * C) return EVF_EINVAL;
+  hipStream_t st = EVF_STREAM(stream);
+  hipLaunchKernelGGL(k_chan_reduce<true>, dim3((unsigned)(bpg * G)), dim3(256), 0, st, x, y, center, scale, mode, G, (long)npg, C,
+                     ldx, ldy, ct, ppb, ws);
+  hipLaunchKernelGGL(k_chan_rowsum, dim3((unsigned)evf_cdiv(C, 64) * G), dim3(64 * CR_RUNS), 0, st, (const float*)ws, (int)bpg, C,
+                     accumulate ? 1 : 0, out);
   return evf_status();
 }
 

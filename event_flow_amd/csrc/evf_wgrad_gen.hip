@@ -32,7 +32,9 @@ struct WgGeo {
   int stages;  // 32-pixel stages per K split
 };
 
-template <int CT, int NT, int VEC, int VG>
+// SLAB (evf_conv2d_wgrad_det): no atomics -- the block stores its tile into gw = slab [split][tap][ci][co] (co fastest: coalesced,
+// as k_wgrad9 does) for k_wgrad_reduce_taps, which adds the splits in a fixed order into the torch layout.
+template <int CT, int NT, int VEC, int VG, bool SLAB = false>
 __global__ __launch_bounds__(256) void k_conv2d_wgrad_f32(const float* __restrict__ x, const float* __restrict__ gy,
                                                           float* __restrict__ gw, float* __restrict__ gbias, WgGeo g) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -183,7 +185,9 @@ __global__ __launch_bounds__(256) void k_conv2d_wgrad_f32(const float* __restric
 #pragma unroll
     for (int w4 = 0; w4 < 4; ++w4) v += red[(w4 * CT * NT + sub) * 1024 + (e & 1023)];
     const int ci = ci0 + c * 32 + ci_l, co = co0 + t * 32 + co_l;
-    if (ci < g.Cin && co < g.Cout && g.cin_off + ci < g.cin_total)
+    if (SLAB) {
+      if (ci < g.Cin && co < g.Cout) gw[(((long)blockIdx.x * T + tap) * g.Cin + ci) * g.Cout + co] = v;
+    } else if (ci < g.Cin && co < g.Cout && g.cin_off + ci < g.cin_total)
       evf_atomic_add(gw + ((long)co * g.cin_total + g.cin_off + ci) * T + tap, v);
   }
   if (do_bias) {
@@ -197,7 +201,7 @@ __global__ __launch_bounds__(256) void k_conv2d_wgrad_f32(const float* __restric
   }
 }
 
-template <int CT, int NT>
+template <int CT, int NT, bool SLAB = false>
 static void wg_launch(const float* x, const float* gy, float* gw, float* gbias, const WgGeo& g, int ksplit, bool vec4,
                       hipStream_t st) {
   const int n_ct = evf_cdiv(g.Cin, 32 * CT), n_nt = evf_cdiv(g.Cout, 32 * NT);
@@ -208,13 +212,13 @@ static void wg_launch(const float* x, const float* gy, float* gw, float* gbias, 
   const bool vg = g.Cout % 4 == 0 && g.ldg % 4 == 0 && ((uintptr_t)gy & 15) == 0;
   (void)vec4;
   if (vx && vg)
-    hipLaunchKernelGGL((k_conv2d_wgrad_f32<CT, NT, 4, 4>), grid, block, smem, st, x, gy, gw, gbias, g);
+    hipLaunchKernelGGL((k_conv2d_wgrad_f32<CT, NT, 4, 4, SLAB>), grid, block, smem, st, x, gy, gw, gbias, g);
   else if (vx)  // e.g. the 32 -> 2 prediction heads
-    hipLaunchKernelGGL((k_conv2d_wgrad_f32<CT, NT, 4, 1>), grid, block, smem, st, x, gy, gw, gbias, g);
+    hipLaunchKernelGGL((k_conv2d_wgrad_f32<CT, NT, 4, 1, SLAB>), grid, block, smem, st, x, gy, gw, gbias, g);
   else if (vg)
-    hipLaunchKernelGGL((k_conv2d_wgrad_f32<CT, NT, 1, 4>), grid, block, smem, st, x, gy, gw, gbias, g);
+    hipLaunchKernelGGL((k_conv2d_wgrad_f32<CT, NT, 1, 4, SLAB>), grid, block, smem, st, x, gy, gw, gbias, g);
   else
-    hipLaunchKernelGGL((k_conv2d_wgrad_f32<CT, NT, 1, 1>), grid, block, smem, st, x, gy, gw, gbias, g);
+    hipLaunchKernelGGL((k_conv2d_wgrad_f32<CT, NT, 1, 1, SLAB>), grid, block, smem, st, x, gy, gw, gbias, g);
 }
 
 
@@ -1109,6 +1113,97 @@ extern "C" int evf_conv2d_wgrad(const float* x, int ldx, const float* g_y, int l
     wg_launch<1, 2>(x, g_y, g_w, g_bias, g, (int)ksplit, vec4, st);
   else
     wg_launch<1, 1>(x, g_y, g_w, g_bias, g, (int)ksplit, vec4, st);
+  return evf_status();
+}
+
+// ---- evf_conv2d_wgrad_det: the weight gradient with every sum in a fixed order (no atomics, no memset of g_w) --------------------
+// 3x3, the 1x1 with at most four outputs and the four-input-channel 3x3 are order-fixed as they stand once no bias is asked for:
+// they forward to evf_conv2d_wgrad with g_bias = NULL.  Every other shape (1x1 with more outputs, 5x5, 7x7) runs
+// k_conv2d_wgrad_f32<.., SLAB> under the default's split rule and k_wgrad_reduce_taps.  The bias gradient is never summed here:
+// it is evf_chan_reduce_det (mode 0, one group) over g_y, so a g_bias is refused.
+//
+// gw[(co*cin_total + cin_off + ci)*T + tap] (+)= sum_split slab[split][tap][ci][co]: the sibling of k_wgrad_reduce for T taps.  A
+// block = 64 outputs x WGR_G runs of consecutive splits: each run is added in split order by one thread, the runs in run order
+// by the first; one plain store per output.
+__global__ __launch_bounds__(64 * WGR_G) void k_wgrad_reduce_taps(const float* __restrict__ slab, int nsplit, int T, int Cin, int Cout,
+                                                                  int cin_total, int cin_off, int accumulate, float* __restrict__ gw) {
+  __shared__ float red[WGR_G][64];
+  const int tx = threadIdx.x & 63, run = threadIdx.x >> 6;
+  const long per = (long)T * Cin * Cout;
+  const long e = (long)blockIdx.x * 64 + tx;
+  const long ec = e < per ? e : per - 1;
+  const float* __restrict__ p = slab + ec;
+  const int len = (nsplit + WGR_G - 1) / WGR_G;
+  const int k0 = run * len, k1 = k0 + len < nsplit ? k0 + len : nsplit;
+  float s = 0.f;
+#pragma unroll 4
+  for (int k = k0; k < k1; ++k) s += p[(long)k * per];
+  red[run][tx] = s;
+  __syncthreads();
+  if (run != 0 || e >= per) return;
+  float a = 0.f;
+#pragma unroll
+  for (int q = 0; q < WGR_G; ++q) a += red[q][tx];
+  const int co = (int)(e % Cout), ci = (int)((e / Cout) % Cin), tap = (int)(e / ((long)Cout * Cin));
+  if (cin_off + ci >= cin_total) return;  // alignment-padding channel of the activation: no weight behind it
+  float* d = gw + ((long)co * cin_total + cin_off + ci) * T + tap;
+  *d = accumulate ? *d + a : a;
+}
+
+// the split rule of evf_conv2d_wgrad's generic-kernel-size path, restated: -> K splits, 32-pixel stages per split
+static int wg_gen_split(int B, int H, int W, int Cin, int Cout, int ksz, int stride, int* stages) {
+  const long M = (long)B * cg_out_dim(H, ksz, stride) * cg_out_dim(W, ksz, stride);
+  const int CT = Cin > 32 ? 2 : 1, NT = Cout > 32 ? 2 : 1;
+  const long tiles = (long)evf_cdiv(Cin, 32 * CT) * evf_cdiv(Cout, 32 * NT) * ksz * ksz;
+  const long st_total = evf_cdiv(M, 32);
+  long ksplit = evf_cdiv(1024, tiles);
+  if (ksplit > st_total / 8) ksplit = st_total / 8;
+  if (ksplit < 1) ksplit = 1;
+  *stages = evf_cdiv(st_total, ksplit);
+  return evf_cdiv(st_total, *stages);
+}
+
+extern "C" int64_t evf_conv2d_wgrad_det_ws(int B, int H, int W, int Cin, int Cout, int ksz, int stride) {
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !EVF_KSZ_OK(ksz) || (stride != 1 && stride != 2)) return 0;
+  int64_t n = evf_conv2d_wgrad_ws(B, H, W, Cin, Cout, ksz, stride);
+  if (ksz != 3) {  // (a 1x1 the streaming kernel turns down for its alignment takes the slab path)
+    int stages;
+    const int64_t m = (int64_t)wg_gen_split(B, H, W, Cin, Cout, ksz, stride, &stages) * ksz * ksz * Cin * Cout;
+    if (m > n) n = m;
+  }
+  return n;
+}
+
+extern "C" int evf_conv2d_wgrad_det(const float* x, int ldx, const float* g_y, int ldg, float* g_w, float* g_bias, int B, int H,
+                                    int W, int Cin, int Cout, int ksz, int stride, int cin_total, int cin_off, int accumulate,
+                                    float* ws, int64_t ws_floats, void* stream) {
+  if (!x || !g_y || !g_w || g_bias || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !EVF_KSZ_OK(ksz) ||
+      (stride != 1 && stride != 2) || ldx < Cin || ldg < Cout || cin_off < 0 || cin_off >= cin_total ||
+      (!(accumulate & 1) && (cin_off != 0 || Cin < cin_total)) || ((uintptr_t)g_y & 15))
+    return EVF_EINVAL;
+  if (!ws || ws_floats < evf_conv2d_wgrad_det_ws(B, H, W, Cin, Cout, ksz, stride)) return EVF_EINVAL;
+  if (ksz == 3 || wg1_small_ok(Cin, Cout, ksz, stride, ldx, x))
+    return evf_conv2d_wgrad(x, ldx, g_y, ldg, g_w, nullptr, B, H, W, Cin, Cout, ksz, stride, cin_total, cin_off, accumulate, ws, stream);
+  hipStream_t st = EVF_STREAM(stream);
+  WgGeo g;
+  g.B = B, g.H = H, g.W = W, g.Cin = Cin, g.Cout = Cout, g.ksz = ksz, g.stride = stride, g.ldx = ldx, g.ldg = ldg;
+  g.cin_total = cin_total, g.cin_off = cin_off;
+  g.OH = cg_out_dim(H, ksz, stride), g.OW = cg_out_dim(W, ksz, stride);
+  const int ksplit = wg_gen_split(B, H, W, Cin, Cout, ksz, stride, &g.stages);
+  const int CT = Cin > 32 ? 2 : 1, NT = Cout > 32 ? 2 : 1;
+  if (CT == 2 && NT == 2)
+    wg_launch<2, 2, true>(x, g_y, ws, nullptr, g, ksplit, false, st);
+  else if (CT == 2)
+    wg_launch<2, 1, true>(x, g_y, ws, nullptr, g, ksplit, false, st);
+  else if (NT == 2)
+    wg_launch<1, 2, true>(x, g_y, ws, nullptr, g, ksplit, false, st);
+  else
+    wg_launch<1, 1, true>(x, g_y, ws, nullptr, g, ksplit, false, st);
+  int rc = evf_status();
+  if (rc) return rc;
+  const long per = (long)ksz * ksz * Cin * Cout;
+  hipLaunchKernelGGL(k_wgrad_reduce_taps, dim3(evf_cdiv(per, 64)), dim3(64 * WGR_G), 0, st, (const float*)ws, ksplit, ksz * ksz, Cin,
+                     Cout, cin_total, cin_off, accumulate & 1, g_w);
   return evf_status();
 }
 

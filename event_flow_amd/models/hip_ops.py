@@ -250,25 +250,83 @@ def _scratch(n, dev, slot=0):
     return buf
 
 
+# Scratch of the deterministic sums of the non-spiking zoo (evf_chan_reduce_det, evf_leaky_bwd_det, evf_conv2d_wgrad_det): per-block
+# partial sums, need not be zero.  One buffer per device per kind, sized by the library's *_ws functions; calls are stream-ordered on
+# ONE stream per device.  Allocated and grown outside any capture only (a tensor made inside one belongs to the capture's memory
+# pool); a buffer that was outgrown stays alive, because captured graphs hold its address.
+DET_WS_MIN_FLOATS = 1 << 16
+_DET_WS = {}
+_DET_WS_RETIRED = []
+
+
+def det_ws_floats(n):
+    """Allocation size for a request of n floats: the next power of two, 64 Ki floats at least (growth stays rare)."""
+    size = DET_WS_MIN_FLOATS
+    while size < n:
+        size <<= 1
+    return size
+
+
+def _det_ws(kind, n, dev):
+    buf = _DET_WS.get((dev, kind))
+    if buf is None or buf.numel() < n:
+        if torch.device(dev).type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise _lib.EvflowError(f"the deterministic {kind} scratch has to grow to {int(n)} floats, which must not happen inside a "
+                                   "capture: run the step eagerly once first")
+        if buf is not None:
+            _DET_WS_RETIRED.append(buf)
+        buf = torch.empty(det_ws_floats(int(n)), dtype=torch.float32, device=dev)
+        _DET_WS[(dev, kind)] = buf
+    return buf
+
+
+def chan_reduce(det, x, ldx, y, ldy, center, scale, mode, G, npg, C, out, accumulate=0):
+    """evf_chan_reduce (out = the sums) or, det, evf_chan_reduce_det (fixed-order sums; accumulate 1 adds onto out)."""
+    if not det:
+        if accumulate:
+            raise _lib.EvflowError("evf_chan_reduce overwrites its output")
+        _lib.call("evf_chan_reduce", _lib.ptr(x), ldx, _lib.ptr(y), ldy, _lib.ptr(center), _lib.ptr(scale), mode, G, npg, C, _lib.ptr(out))
+        return
+    ws = _det_ws("chan", _lib.load().evf_chan_reduce_det_ws(G, npg, C), x.device)
+    _lib.call("evf_chan_reduce_det", _lib.ptr(x), ldx, _lib.ptr(y), ldy, _lib.ptr(center), _lib.ptr(scale), mode, G, npg, C,
+              _lib.ptr(out), 1 if accumulate else 0, _lib.ptr(ws), ws.numel())
+
+
 def conv_wgrad(x, g_y, g_w, g_b, Cin, Cout, k, stride, cin_total=None, cin_off=0, accumulate=0, spikes=False, analog_head=0,
-               exact_from=None):
+               exact_from=None, det=None):
     """Weight (+ bias) gradient.  spikes: x is spike-valued (binary spikes, counts, bilinear blends of spikes): the 3x3
     stride-1 contraction runs on the bf16 matrix cores (exact there; anything else it finds is redone in fp32).
     analog_head: the first `analog_head` channels of x are real-valued (a decoder's flow prediction): they are split off
     into an fp32 call of their own so that the rest stays on the fast path.
     exact_from: provenance (spike_tag below) -- the channels of x from this index on are exactly representable in bf16 BY
-    CONSTRUCTION: the bf16 kernel then reduces its own partial sums (one launch instead of three; evf_conv2d_wgrad bit 2)."""
+    CONSTRUCTION: the bf16 kernel then reduces its own partial sums (one launch instead of three; evf_conv2d_wgrad bit 2).
+    det: the deterministic switch as the calling Function recorded it in its forward (None: as it stands now) -- the weight
+    gradient through evf_conv2d_wgrad_det without a bias, the bias gradient ONCE (whatever the split below) through
+    evf_chan_reduce_det over g_y."""
     B, H, W = x.shape[0], x.shape[1], x.shape[2]
     ct = Cin if cin_total is None else cin_total
+    if det is None:
+        det = _lib.deterministic()
+    if det and g_b is not None:
+        conv_wgrad(x, g_y, g_w, None, Cin, Cout, k, stride, cin_total, cin_off, accumulate, spikes, analog_head, exact_from, det=True)
+        chan_reduce(True, g_y, g_y.stride(2), None, 0, None, None, 0, 1, g_y.shape[0] * g_y.shape[1] * g_y.shape[2], Cout, g_b,
+                    accumulate & 1)
+        return
     if spikes and analog_head and k == 3 and stride == 1 and cin_off == 0 and Cin > 8:
         a = (analog_head + 3) // 4 * 4  # (the tail must stay 16-byte aligned)
         if not accumulate:
             _lib.zero_(g_w)
             if g_b is not None:
                 _lib.zero_(g_b)
-        conv_wgrad(x, g_y, g_w, g_b, a, Cout, k, stride, ct, 0, 1, spikes=False)
+        conv_wgrad(x, g_y, g_w, g_b, a, Cout, k, stride, ct, 0, 1, spikes=False, det=det)
         conv_wgrad(x[..., a:], g_y, g_w, None, Cin - a, Cout, k, stride, ct, a, 1, spikes=True,
-                   exact_from=None if exact_from is None else max(exact_from - a, 0))
+                   exact_from=None if exact_from is None else max(exact_from - a, 0), det=det)
+        return
+    if det:
+        ws = _det_ws("wgrad", _lib.load().evf_conv2d_wgrad_det_ws(B, H, W, Cin, Cout, k, stride), x.device)
+        exact = 4 if (spikes and EXACT_WGRAD and exact_from is not None and exact_from <= 0) else 0
+        _lib.call("evf_conv2d_wgrad_det", _lib.ptr_strided(x), x.stride(2), _lib.ptr(g_y), g_y.stride(2), _lib.ptr(g_w), None,
+                  B, H, W, Cin, Cout, k, stride, ct, cin_off, (accumulate & 1) | (0 if spikes else 2) | exact, _lib.ptr(ws), ws.numel())
         return
     ws = _scratch(_lib.load().evf_conv2d_wgrad_ws(B, H, W, Cin, Cout, k, stride), x.device)
     exact = 4 if (spikes and EXACT_WGRAD and exact_from is not None and exact_from <= 0) else 0
@@ -629,21 +687,21 @@ class _CellStep(torch.autograd.Function):
             d = bound_grad(wff)
             head = int(getattr(cell, "analog_input_channels", 0))  # (a decoder's flow-prediction channels, models/unet.py)
             if d is not None:
-                conv_wgrad(xn, g_cur, d, None, Cin, C, k, s, cin_total=wff.shape[1], accumulate=1, spikes=True, analog_head=head,
+                conv_wgrad(xn, g_cur, d, None, Cin, C, k, s, cin_total=wff.shape[1], accumulate=1, spikes=True, analog_head=head, det=ctx.det,
                            exact_from=ctx.exact_from)
             else:
                 g_wff = _new(tuple(wff.shape), dev)
-                conv_wgrad(xn, g_cur, g_wff, None, Cin, C, k, s, cin_total=wff.shape[1], spikes=True, analog_head=head,
+                conv_wgrad(xn, g_cur, g_wff, None, Cin, C, k, s, cin_total=wff.shape[1], spikes=True, analog_head=head, det=ctx.det,
                            exact_from=ctx.exact_from)
         if cell.recurrent and need[5]:
             d = bound_grad(wrec)
             # (the recurrent input is the cell's own previous SPIKES unless group norm rescaled them: exact by construction)
             rec_exact = 0 if ctx.rec_spikes else None
             if sp is not None and d is not None:
-                conv_wgrad(sp[1], g_cur, d, None, C, C, k, 1, accumulate=1, spikes=True, exact_from=rec_exact)
+                conv_wgrad(sp[1], g_cur, d, None, C, C, k, 1, accumulate=1, spikes=True, exact_from=rec_exact, det=ctx.det)
             elif sp is not None:
                 g_wrec = _new(tuple(wrec.shape), dev)
-                conv_wgrad(sp[1], g_cur, g_wrec, None, C, C, k, 1, spikes=True, exact_from=rec_exact)
+                conv_wgrad(sp[1], g_cur, g_wrec, None, C, C, k, 1, spikes=True, exact_from=rec_exact, det=ctx.det)
             elif d is None:
                 g_wrec = _lib.zeros(tuple(wrec.shape), dtype=torch.float32, device=dev)
         if need[1]:
@@ -770,6 +828,7 @@ class _ConvAct(torch.autograd.Function):
         B, H, W, Cin = xn.shape
         Cout, _, k, _ = weight.shape
         Ho, Wo = _out_dim(H, k, stride), _out_dim(W, k, stride)
+        ctx.det = _lib.deterministic()  # (the backward follows the switch as it stood here: the _CellStep rule)
         ctx.head1 = _head1x1_ok(Cin, Cout, k, stride, residual, weight)
         if ctx.head1:  # a 1x1 layer with a handful of outputs (the flow predictions): one streaming kernel each way
             y = _new((B, H, W, Cout), xn.device)
@@ -831,11 +890,11 @@ class _ConvAct(torch.autograd.Function):
         if need[2] or (ctx.has_bias and need[3]):
             d_w, d_b = bound_grad(weight), bound_grad(ctx.bias) if ctx.has_bias else None
             if d_w is not None and (not ctx.has_bias or d_b is not None):
-                conv_wgrad(xn, g, d_w, d_b, Cin, Cout, k, ctx.stride, cin_total=weight.shape[1], accumulate=1)
+                conv_wgrad(xn, g, d_w, d_b, Cin, Cout, k, ctx.stride, cin_total=weight.shape[1], accumulate=1, det=ctx.det)
             else:
                 g_w = _new(tuple(weight.shape), g.device)
                 g_b = _new((Cout,), g.device) if ctx.has_bias else None
-                conv_wgrad(xn, g, g_w, g_b, Cin, Cout, k, ctx.stride, cin_total=weight.shape[1])
+                conv_wgrad(xn, g, g_w, g_b, Cin, Cout, k, ctx.stride, cin_total=weight.shape[1], det=ctx.det)
         if need[1]:
             g_xn = _new((B, H, W, Cin), g.device)
             conv_dgrad(g, _wcache(ctx.owner, "wT").get(weight, 1, 0, Cin), g_xn, Cin, Cout, k, ctx.stride)
@@ -897,12 +956,13 @@ class _Norm2d(torch.autograd.Function):
         G, npg = (B, H * W) if instance else (1, B * H * W)
         dev = xn.device
         eps = float(layer.eps)
+        ctx.det = _lib.deterministic()
         if use_input_stats:
             s1 = _new((G, C), dev)
-            _lib.call("evf_chan_reduce", _lib.ptr(xn), C, None, 0, None, None, 0, G, npg, C, _lib.ptr(s1))
+            chan_reduce(ctx.det, xn, C, None, 0, None, None, 0, G, npg, C, s1)
             mean = s1 / npg
             s2 = _new((G, C), dev)
-            _lib.call("evf_chan_reduce", _lib.ptr(xn), C, None, 0, _lib.ptr(mean), None, 1, G, npg, C, _lib.ptr(s2))
+            chan_reduce(ctx.det, xn, C, None, 0, mean, None, 1, G, npg, C, s2)
             var = s2 / npg  # biased: what normalises
             if layer.track_running_stats and layer.running_mean is not None:
                 with torch.no_grad():
@@ -935,8 +995,8 @@ class _Norm2d(torch.autograd.Function):
         dev = g.device
         s1 = _new((G, C), dev)  # sum g
         s2 = _new((G, C), dev)  # sum g * xhat
-        _lib.call("evf_chan_reduce", _lib.ptr(g), C, None, 0, None, None, 0, G, npg, C, _lib.ptr(s1))
-        _lib.call("evf_chan_reduce", _lib.ptr(xn), C, _lib.ptr(g), C, _lib.ptr(mean), _lib.ptr(rstd), 2, G, npg, C, _lib.ptr(s2))
+        chan_reduce(ctx.det, g, C, None, 0, None, None, 0, G, npg, C, s1)
+        chan_reduce(ctx.det, xn, C, g, C, mean, rstd, 2, G, npg, C, s2)
         A = (w * rstd).contiguous()
         if stats:  # the statistics depend on x
             Bc = (-(rstd * rstd) * w * s2 / npg).contiguous()
@@ -962,11 +1022,12 @@ class _GroupNorm1(torch.autograd.Function):
         B, H, W, C = xn.shape
         npg, dev = H * W, xn.device
         N = float(C * npg)
+        ctx.det = _lib.deterministic()
         s1 = _new((B, C), dev)
-        _lib.call("evf_chan_reduce", _lib.ptr(xn), C, None, 0, None, None, 0, B, npg, C, _lib.ptr(s1))
+        chan_reduce(ctx.det, xn, C, None, 0, None, None, 0, B, npg, C, s1)
         mean = (s1.sum(1, keepdim=True) / N).expand(B, C).contiguous()
         s2 = _new((B, C), dev)
-        _lib.call("evf_chan_reduce", _lib.ptr(xn), C, None, 0, _lib.ptr(mean), None, 1, B, npg, C, _lib.ptr(s2))
+        chan_reduce(ctx.det, xn, C, None, 0, mean, None, 1, B, npg, C, s2)
         rstd = torch.rsqrt(s2.sum(1, keepdim=True) / N + eps).expand(B, C).contiguous()
         w = weight.detach().float().reshape(1, C)
         b = bias.detach().float().reshape(1, C)
@@ -987,8 +1048,8 @@ class _GroupNorm1(torch.autograd.Function):
         g = to_nhwc(g_y)
         s1 = _new((B, C), dev)  # sum g
         s2 = _new((B, C), dev)  # sum g * xhat
-        _lib.call("evf_chan_reduce", _lib.ptr(g), C, None, 0, None, None, 0, B, npg, C, _lib.ptr(s1))
-        _lib.call("evf_chan_reduce", _lib.ptr(xn), C, _lib.ptr(g), C, _lib.ptr(mean), _lib.ptr(rstd), 2, B, npg, C, _lib.ptr(s2))
+        chan_reduce(ctx.det, g, C, None, 0, None, None, 0, B, npg, C, s1)
+        chan_reduce(ctx.det, xn, C, g, C, mean, rstd, 2, B, npg, C, s2)
         S1 = (w * s1).sum(1, keepdim=True)
         S2 = (w * s2).sum(1, keepdim=True)
         A = (w * rstd).contiguous()
@@ -1032,6 +1093,7 @@ class _ConvTranspose(torch.autograd.Function):
         if bias is not None:
             y += bias.detach().reshape(1, 1, 1, Co)
         ctx.owner = owner
+        ctx.det = _lib.deterministic()
         ctx.saved = (xn, weight)
         ctx.has_bias = bias is not None
         return from_nhwc(y)
@@ -1050,7 +1112,7 @@ class _ConvTranspose(torch.autograd.Function):
             g_x = from_nhwc(gxn)
         if need[2]:
             g_w = _new(tuple(weight.shape), g.device)
-            conv_wgrad(g, xn, g_w, None, Co, Ci, k, 2, cin_total=Co)
+            conv_wgrad(g, xn, g_w, None, Co, Ci, k, 2, cin_total=Co, det=ctx.det)
         if ctx.has_bias and need[3]:
             g_b = g.sum((0, 1, 2))
         return None, g_x, g_w, g_b
@@ -1080,6 +1142,7 @@ class _LeakyMix(torch.autograd.Function):
         _lib.call("evf_leaky_fwd", _lib.ptr(cn), _lib.ptr(pn), _lib.ptr(rn), _lib.ptr(lk), act, B * H * W, C, _lib.ptr(mix),
                   _lib.ptr(out))
         ctx.act, ctx.leak = act, leak
+        ctx.det = _lib.deterministic()
         ctx.saved = (mix, pn, lk)
         ctx.has = (prev is not None, residual is not None)
         if act == 0:
@@ -1102,8 +1165,13 @@ class _LeakyMix(torch.autograd.Function):
         if need[3]:
             d_leak = bound_grad(ctx.leak)
             g_leak = d_leak.view(-1) if d_leak is not None else _lib.zeros(C, dtype=torch.float32, device=mix.device)
-        _lib.call("evf_leaky_bwd", _lib.ptr(gon), _lib.ptr(gmn), _lib.ptr(mix), _lib.ptr(pn), _lib.ptr(lk), ctx.act, B * H * W, C,
-                  _lib.ptr(g_cur), _lib.ptr(g_prev), _lib.ptr(g_leak))
+        if ctx.det:  # the fixed-order twin, its scratch followed by the size
+            ws = _det_ws("leaky", _lib.load().evf_leaky_bwd_det_ws(B * H * W, C), mix.device)
+            _lib.call("evf_leaky_bwd_det", _lib.ptr(gon), _lib.ptr(gmn), _lib.ptr(mix), _lib.ptr(pn), _lib.ptr(lk), ctx.act, B * H * W, C,
+                      _lib.ptr(g_cur), _lib.ptr(g_prev), _lib.ptr(g_leak), _lib.ptr(ws), ws.numel())
+        else:
+            _lib.call("evf_leaky_bwd", _lib.ptr(gon), _lib.ptr(gmn), _lib.ptr(mix), _lib.ptr(pn), _lib.ptr(lk), ctx.act, B * H * W, C,
+                      _lib.ptr(g_cur), _lib.ptr(g_prev), _lib.ptr(g_leak))
         gc = from_nhwc(g_cur)
         return (gc if need[0] else None, from_nhwc(g_prev) if g_prev is not None else None,
                 gc if (ctx.has[1] and need[2]) else None,
@@ -1149,6 +1217,7 @@ class _ConvGRU(torch.autograd.Function):
         o, new = _new((B, H, W, Ch), dev), _new((B, H, W, Ch), dev)
         _lib.call("evf_gru_out_fwd", _lib.ptr(co), _lib.ptr(hn), _lib.ptr(u), n, _lib.ptr(o), _lib.ptr(new))
         ctx.owner = owner
+        ctx.det = _lib.deterministic()
         ctx.biases = (br, bu, bo)
         ctx.saved = (xn, hn, u, r, hr, o, wr, wu, wo)
         return from_nhwc(new)
@@ -1179,9 +1248,9 @@ class _ConvGRU(torch.autograd.Function):
             direct = d_w is not None and d_b is not None
             g_w = d_w if direct else _lib.zeros(tuple(w.shape), dtype=torch.float32, device=dev)
             g_b = d_b if direct else _lib.zeros((Ch,), dtype=torch.float32, device=dev)
-            conv_wgrad(xn, gate_g, g_w, g_b, Cx, Ch, k, 1, cin_total=Cx + Ch, cin_off=0, accumulate=1)
+            conv_wgrad(xn, gate_g, g_w, g_b, Cx, Ch, k, 1, cin_total=Cx + Ch, cin_off=0, accumulate=1, det=ctx.det)
             if hsrc is not None:
-                conv_wgrad(hsrc, gate_g, g_w, None, Ch, Ch, k, 1, cin_total=Cx + Ch, cin_off=Cx, accumulate=1)
+                conv_wgrad(hsrc, gate_g, g_w, None, Ch, Ch, k, 1, cin_total=Cx + Ch, cin_off=Cx, accumulate=1, det=ctx.det)
             return (None, None) if direct else (g_w, g_b)
 
         g_wo, g_bo = wgrads(wo, ctx.biases[2], g_co, hr if hn is not None else None)
@@ -1226,6 +1295,7 @@ class _ConvLSTM(torch.autograd.Function):
         new_c, new_h = _new((B, H, W, Ch), dev), _new((B, H, W, Ch), dev)
         _lib.call("evf_lstm_fwd", _lib.ptr(gates), _lib.ptr(cn), B * H * W, Ch, _lib.ptr(new_c), _lib.ptr(new_h))
         ctx.owner, ctx.bias = owner, b
+        ctx.det = _lib.deterministic()
         ctx.saved = (xn, hn, cn, gates, new_c, w)
         return from_nhwc(new_h), from_nhwc(new_c)
 
@@ -1251,9 +1321,9 @@ class _ConvLSTM(torch.autograd.Function):
             direct = d_w is not None and d_b is not None
             g_w = d_w if direct else _lib.zeros(tuple(w.shape), dtype=torch.float32, device=dev)
             g_b = d_b if direct else _lib.zeros((4 * Ch,), dtype=torch.float32, device=dev)
-            conv_wgrad(xn, g_gates, g_w, g_b, Cx, 4 * Ch, k, 1, cin_total=Cx + Ch, cin_off=0, accumulate=1)
+            conv_wgrad(xn, g_gates, g_w, g_b, Cx, 4 * Ch, k, 1, cin_total=Cx + Ch, cin_off=0, accumulate=1, det=ctx.det)
             if hn is not None:
-                conv_wgrad(hn, g_gates, g_w, None, Ch, 4 * Ch, k, 1, cin_total=Cx + Ch, cin_off=Cx, accumulate=1)
+                conv_wgrad(hn, g_gates, g_w, None, Ch, 4 * Ch, k, 1, cin_total=Cx + Ch, cin_off=Cx, accumulate=1, det=ctx.det)
             if direct:
                 g_w = g_b = None
         g_x = g_hid = None

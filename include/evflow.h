@@ -753,6 +753,19 @@ int64_t evf_conv2d_wgrad_ws(int B, int H, int W, int Cin, int Cout, int ksz, int
 int evf_conv2d_wgrad(const float* x, int ldx, const float* g_y, int ldg, float* g_w, float* g_bias, int B,
                      int H, int W, int Cin, int Cout, int ksz, int stride, int cin_total, int cin_off,
                      int accumulate, float* ws, void* stream);
+/* The deterministic form of evf_conv2d_wgrad: the same arguments, `ws` followed by its size in floats.  Every sum in a fixed
+ * order, no atomics, no memset of g_w.  3x3, the 1x1 with Cout <= 4 the streaming kernel serves and the four-input-channel 3x3
+ * are order-fixed once no bias is asked for and forward to evf_conv2d_wgrad with g_bias = NULL (the four-input-channel kernel is
+ * then eligible where the default call with a bias would not take it).  Every other shape (1x1, 5x5, 7x7) runs the split-K
+ * matrix-core kernel under the default's split rule with plain stores into ws [split][tap][ci][co]; a second launch adds the
+ * splits (16 runs of consecutive splits per output, then the runs in run order) into the torch layout, honouring cin_total /
+ * cin_off / accumulate.  The bias gradient is NOT summed here -- it is evf_chan_reduce_det (mode 0, G = 1) over g_y -- and a
+ * non-null g_bias is refused.  ws: mandatory, >= evf_conv2d_wgrad_det_ws() floats = max(evf_conv2d_wgrad_ws(), splits * k * k *
+ * Cin * Cout) (0 for arguments the call refuses), need not be zero.  EVF_EINVAL before anything is launched. */
+int64_t evf_conv2d_wgrad_det_ws(int B, int H, int W, int Cin, int Cout, int ksz, int stride);
+int evf_conv2d_wgrad_det(const float* x, int ldx, const float* g_y, int ldg, float* g_w, float* g_bias, int B,
+                         int H, int W, int Cin, int Cout, int ksz, int stride, int cin_total, int cin_off,
+                         int accumulate, float* ws, int64_t ws_floats, void* stream);
 
 /* Batch / instance normalisation of NHWC activations (nn.BatchNorm2d / nn.InstanceNorm2d(track_running_stats=True) of the
  * reference's ANN layers, models/submodules.py:46-56, 122-132, 169-180, 273-301) = two per-element passes; the per-channel
@@ -762,6 +775,16 @@ int evf_conv2d_wgrad(const float* x, int ldx, const float* g_y, int ldg, float* 
  *   evf_chan_affine: out = (g ? A*g : 0) + Bc*x + Cc with per-(group, channel) coefficients [G*C]. */
 int evf_chan_reduce(const float* x, int ldx, const float* y, int ldy, const float* center, const float* scale, int mode,
                     int G, int64_t npg, int C, float* out, void* stream);
+/* The deterministic form of evf_chan_reduce: its arguments, then `accumulate` (0: out = sum, 1: out += sum), `ws` and its size
+ * in floats.  The same three modes, block shape and blocks-per-group rule; no atomics and no memset: block b of group g stores
+ * its C sums as row b of ws [G][blocks per group][C], a second launch adds a column's rows (16 runs of consecutive rows, each
+ * in row order, then the runs in run order) and writes the output once.  With mode 0, G = 1 over g_y [M][ldg] this is the
+ * bias gradient of a convolution in deterministic mode.  ws: mandatory, >= evf_chan_reduce_det_ws(G, npg, C) floats (0 for
+ * arguments the call refuses), need not be zero, contents unspecified afterwards.  EVF_EINVAL for everything evf_chan_reduce
+ * refuses and for a null or short ws, before anything is launched. */
+int64_t evf_chan_reduce_det_ws(int G, int64_t npg, int C);
+int evf_chan_reduce_det(const float* x, int ldx, const float* y, int ldy, const float* center, const float* scale, int mode,
+                        int G, int64_t npg, int C, float* out, int accumulate, float* ws, int64_t ws_floats, void* stream);
 /* Weight normalisation of a conv weight [Cout][n = Cin * k * k] (norm = "weight" cells: models/spiking_submodules.py:87-88,
  * :502-504, nn.utils.weight_norm with dim = 0):  w[o] = v[o] * g[o] / ||v[o]||; nrm [Cout] keeps the norms for the backward, which
  * maps dL/dw to dL/dv [Cout][n] and dL/dg [Cout]. */
@@ -868,6 +891,16 @@ int evf_leaky_fwd(const float* cur, const float* prev, const float* residual, co
                   float* mix, float* out, void* stream);
 int evf_leaky_bwd(const float* g_out, const float* g_state, const float* mix, const float* prev, const float* leak, int act,
                   int64_t npix, int C, float* g_cur, float* g_prev, float* g_leak, void* stream);
+/* The deterministic form of evf_leaky_bwd: the same arguments, then `ws` and its size in floats.  g_cur / g_prev are
+ * bit-identical to evf_leaky_bwd's (same body, block size, grid and trips); g_leak (+= onto its contents, single writer, null
+ * = skip) is a function of the arguments alone: a block adds its C sums in LDS in index order and stores them as row blockIdx
+ * of ws [blocks][C], a second launch adds the rows as evf_neuron_bwd_det's does.  The replica array of evf_leaky_bwd is not
+ * touched.  ws: mandatory, >= evf_leaky_bwd_det_ws(npix, C) floats (0 for arguments the call refuses; at most 1024 * 1024),
+ * need not be zero.  EVF_EINVAL for everything evf_leaky_bwd refuses and for a null or short ws, before anything is launched. */
+int64_t evf_leaky_bwd_det_ws(int64_t npix, int C);
+int evf_leaky_bwd_det(const float* g_out, const float* g_state, const float* mix, const float* prev, const float* leak, int act,
+                      int64_t npix, int C, float* g_cur, float* g_prev, float* g_leak, float* ws, int64_t ws_floats,
+                      void* stream);
 
 /* Stand-alone spike functions (models/spiking_util.py:13-25 forward, :38-93 surrogates): z = (x - thresh > 0)
  * as fp32; g_x = g * surrogate(x - thresh, width) with surrogate = EVF_ARCTAN / SUPERSPIKE / TRIANGLE / MULTIGAUSS.
