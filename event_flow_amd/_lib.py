@@ -30,6 +30,9 @@ SIGNATURES = {
     "evf_interpolate": [P, P, P, I, I, I, I, I, P, P],
     "evf_cm_smooth_blocks": [I, I, I, I],
     "evf_norm_nonzero": [P, ctypes.c_int64, P, P, P],
+    # the deterministic form: per-block partial sums in ws (doubles), followed by its size
+    "evf_norm_nonzero_det_ws": [L],
+    "evf_norm_nonzero_det": [P, L, P, P, L, P],
     "evf_cm_loss_ws": [I, I, I, I, I],
     "evf_cm_loss_fwd": [P, P, P, P, P, I, I, I, I, I, I, F, F, I, P, P, P, P, P, P],
     "evf_cm_loss_bwd": [P, P, P, P, P, I, I, I, I, I, I, F, F, I, P, P, P, P, P, P],
@@ -81,6 +84,8 @@ NETWORK_SIGNATURES = {
     "evf_defer_profile": [I],
     "evf_defer_profile_read": [P, P],
     "evf_lif_bwd": [P, P, P, P, P, P, P, I, I, I, I, I, F, P, P, P, P, P],
+    # the deterministic form: evf_lif_bwd's arguments, then the pitch and the row count of the per-block rows
+    "evf_lif_bwd_det": [P, P, P, P, P, P, P, I, I, I, I, I, F, P, P, P, P, I, I, P],
     "evf_lif_bwd_wgrad_slabs": [I, I, I],
     "evf_head_lif_bwd_wgrad_slabs": [I, I, I],
     "evf_head_lif_bwd_wgrad": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P, P, P, P, P, I, P],
@@ -123,6 +128,9 @@ NETWORK_SIGNATURES = {
     "evf_conv_wgrad_slabs": [I, I, I],
     "evf_reduce_slabs": [P, I, I, I, P, P],
     "evf_head_wgrad": [P, P, I, I, I, I, P, P],
+    # the deterministic form: a slab row per block instead of dw, then accumulate
+    "evf_head_wgrad_det_slabs": [I, I, I],
+    "evf_head_wgrad_det": [P, P, I, I, I, I, P, I, P],
     "evf_pred_fwd": [P, P, P, I, I, I, P, P],
     "evf_pred_bwd": [P, P, P, P, I, I, I, P, P, P, P],
     "evf_bits_to_nchw": [P, I, I, I, P, P],
@@ -200,7 +208,8 @@ NETWORK_SIGNATURES = {
 }
 RESTYPES = {"evf_head1x1_ws": ctypes.c_int64, "evf_comm_last_error": ctypes.c_char_p, "evf_conv2d_packed_size": ctypes.c_int64, "evf_conv2d_b3_packed_size": ctypes.c_int64, "evf_conv2d_b3_ws": ctypes.c_int64, "evf_conv2d_wgrad_ws": ctypes.c_int64, "evf_cm_loss_ws": ctypes.c_int64, "evf_cm_loss_ws_det": ctypes.c_int64, "evf_cm_loss_bwd_ws_det": ctypes.c_int64,
             "evf_neuron_bwd_det_ws": ctypes.c_int64, "evf_clip_adam_det_ws": ctypes.c_int64,
-            "evf_chan_reduce_det_ws": ctypes.c_int64, "evf_leaky_bwd_det_ws": ctypes.c_int64, "evf_conv2d_wgrad_det_ws": ctypes.c_int64}
+            "evf_chan_reduce_det_ws": ctypes.c_int64, "evf_leaky_bwd_det_ws": ctypes.c_int64, "evf_conv2d_wgrad_det_ws": ctypes.c_int64,
+            "evf_norm_nonzero_det_ws": ctypes.c_int64}
 SIGNATURES.update(NETWORK_SIGNATURES)
 
 _lib = None
@@ -209,7 +218,9 @@ _lib = None
 # evf_cm_loss_fwd_det / evf_cm_loss_bwd_det, voxel grids through evf_encode_events_det / evf_encode_window_det and every
 # iwe_splat through evf_iwe_splat_det (exact, order-independent sums) instead of the float atomics; the spiking cells of the
 # general path through evf_neuron_bwd_det and the two-launch optimizer step through evf_clip_adam_step_det (fixed-order sums);
-# the non-spiking layers through evf_conv2d_wgrad_det, evf_chan_reduce_det and evf_leaky_bwd_det.
+# the non-spiking layers through evf_conv2d_wgrad_det, evf_chan_reduce_det and evf_leaky_bwd_det; norm_input through
+# evf_norm_nonzero_det and the fused FireNet engine's head layer with a voxel input (any channel count but two) through
+# evf_lif_bwd_det and evf_head_wgrad_det (per-block partial sums, added in a fixed order).
 # A switch of this module, not of the library: the C ABI has one entry point per form.
 _deterministic = os.environ.get("EVF_DETERMINISTIC", "0") == "1"
 
@@ -221,8 +232,10 @@ def set_deterministic(on):
     The non-spiking layers of the general path follow the same rule: every weight gradient through evf_conv2d_wgrad_det, every
     bias gradient and every statistic of batch / instance / group norm through evf_chan_reduce_det, the leaky cells' g_leak through
     evf_leaky_bwd_det (fixed-order sums).
-    Not covered: norm_input, events_to_image(accumulate=True) with arbitrary values, the materialising interpolate, k_head_wgrad
-    for voxel inputs on the fused engine."""
+    norm_input (every model) goes through evf_norm_nonzero_det, and a fused FireNet whose input has another channel count than
+    two (voxel encodings) runs its head layer's backward through evf_lif_bwd_det and evf_head_wgrad_det; the engine records the
+    switch with the tape, so the backward follows the forward.  A route that would still add with float atomics raises.
+    Not covered: events_to_image(accumulate=True) with arbitrary values and the materialising interpolate."""
     global _deterministic
     _deterministic = bool(on)
 
@@ -306,6 +319,7 @@ _PROF_VARIANT = {
     "evf_lif_bwd_wgrad": lambda a: "rec" if a[6] is not None else "ff",
     "evf_lif_bwd_wgrad2": lambda a: ("rec" if a[7] is not None else "ff") + ("+2" if a[1] is not None else ""),
     "evf_conv_dgrad_b3_f32": lambda a: "acc" if a[3] else "",
+    "evf_sum_rows": lambda a: "acc" if (a[3] & 1) else "set",  # (acc: from 128 rows on the float-atomic form, k_sum_rows_acc)
     "evf_conv_dgrad_b3_f32_pair": lambda a: "acc" if a[3] else "",
     # general convs: the shape is the variant ("B,H,W,Cin,Cout,k,stride"): bench.py derives the FLOP of every launch from it
     "evf_conv2d_fwd": lambda a: ",".join(str(int(v)) for v in a[6:13]),

@@ -2432,3 +2432,74 @@ extern "C" int evf_norm_nonzero(const float* x, int64_t n, float* out, double* w
   hipLaunchKernelGGL(k_nz_apply, dim3(nb), dim3(256), 0, st, x, (long)n, ws3, out);
   return evf_status();
 }
+
+// The fixed-order twin (evf_norm_nonzero_det): ws = three arrays of nb doubles -- per-block sums, counts, sums of squared
+// deviations.  Block b plain-stores element b; the next launch's blocks each add ALL nb elements themselves, in one order that
+// is a function of nb alone (nz_total), so every block holds the same bits.  No memset, no atomic, nobody waits for a block.
+__device__ __forceinline__ double nz_block_sum(double s, double* red) {  // -> the block's sum, in every thread
+  for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o, 64);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  __syncthreads();  // (red may still be read from the call before)
+  if (lane == 0) red[wv] = s;
+  __syncthreads();
+  double t = 0.0;
+  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
+  return t;
+}
+// sum of a[0 .. nb): thread t adds a[t], a[t + 256], ... in index order, then the butterfly and the four waves in order.  a + b
+// and b + a are the same bits, so all lanes, all threads and all blocks end with one value.
+__device__ __forceinline__ double nz_total(const double* __restrict__ a, int nb, double* red) {
+  double s = 0.0;
+  for (int k = threadIdx.x; k < nb; k += blockDim.x) s += a[k];
+  return nz_block_sum(s, red);
+}
+__global__ __launch_bounds__(256) void k_nz_sum_det(const float* __restrict__ x, long n, double* __restrict__ ws) {
+  __shared__ double red[4];
+  double s = 0.0, c = 0.0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float v = x[i];
+    if (v != 0.f) s += (double)v, c += 1.0;
+  }
+  const double ts = nz_block_sum(s, red), tc = nz_block_sum(c, red);
+  if (threadIdx.x == 0) ws[blockIdx.x] = ts, ws[gridDim.x + blockIdx.x] = tc;
+}
+__global__ __launch_bounds__(256) void k_nz_dev_det(const float* __restrict__ x, long n, double* __restrict__ ws) {
+  __shared__ double red[4];
+  const int nb = gridDim.x;
+  const double ts = nz_total(ws, nb, red), tc = nz_total(ws + nb, nb, red);
+  const double mean = ts / tc;
+  double s = 0.0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float v = x[i];
+    if (v != 0.f) {
+      const double d = (double)v - mean;
+      s += d * d;
+    }
+  }
+  const double td = nz_block_sum(s, red);
+  if (threadIdx.x == 0) ws[2 * nb + blockIdx.x] = td;
+}
+__global__ __launch_bounds__(256) void k_nz_apply_det(const float* __restrict__ x, long n, const double* __restrict__ ws,
+                                                      float* __restrict__ out) {
+  __shared__ double red[4];
+  const int nb = gridDim.x;
+  const double ts = nz_total(ws, nb, red), tc = nz_total(ws + nb, nb, red), td = nz_total(ws + 2 * nb, nb, red);
+  const float mean = (float)(ts / tc);
+  const float sd = (float)sqrt(td / (tc - 1.0));  // unbiased; one non-zero entry -> NaN like torch
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float v = x[i];
+    out[i] = v != 0.f ? (v - mean) / sd : 0.f;
+  }
+}
+
+static int nz_blocks(int64_t n) { return (int)((n + 1023) / 1024 < 1024 ? (n + 1023) / 1024 : 1024); }
+extern "C" int64_t evf_norm_nonzero_det_ws(int64_t n) { return n > 0 ? 3 * (int64_t)nz_blocks(n) : 0; }
+extern "C" int evf_norm_nonzero_det(const float* x, int64_t n, float* out, double* ws, int64_t ws_doubles, void* stream) {
+  if (!x || !out || !ws || n <= 0 || ws_doubles < evf_norm_nonzero_det_ws(n)) return EVF_EINVAL;
+  hipStream_t st = EVF_STREAM(stream);
+  const int nb = nz_blocks(n);
+  hipLaunchKernelGGL(k_nz_sum_det, dim3(nb), dim3(256), 0, st, x, (long)n, ws);
+  hipLaunchKernelGGL(k_nz_dev_det, dim3(nb), dim3(256), 0, st, x, (long)n, ws);
+  hipLaunchKernelGGL(k_nz_apply_det, dim3(nb), dim3(256), 0, st, x, (long)n, ws, out);
+  return evf_status();
+}

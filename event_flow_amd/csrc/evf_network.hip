@@ -1028,12 +1028,15 @@ __device__ __forceinline__ float evf_surrogate(int kind, float x, float width) {
   }
 }
 
+// DET (evf_lif_bwd_det): g_leak / g_thresh address row 0 of a [blocks][row_ld] buffer and block b adds its 32 + 32 channel sums
+// to row b by plain read-modify-write (the convention of k_lif_bwd_wgrad's rows) -- no atomic; the element-wise part is the same
+template <bool DET>
 __global__ __launch_bounds__(256) void k_lif_bwd(const float4* __restrict__ g_z_out, const float4* __restrict__ g_v_out,
                           const float4* __restrict__ v_out, const float4* __restrict__ v_prev,
                           const uint32_t* __restrict__ z_prev, const float* __restrict__ leak,
                           const float* __restrict__ thresh, long npix, int hard_reset, int surrogate, float width,
                           float4* __restrict__ g_cur, float4* __restrict__ g_v_prev, float* __restrict__ g_leak,
-                          float* __restrict__ g_thresh) {
+                          float* __restrict__ g_thresh, int row_ld) {
   __shared__ float s_red[2][4][C32];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int cg = tid & 7;  // channel group: channels 4cg..4cg+3
@@ -1110,9 +1113,11 @@ __global__ __launch_bounds__(256) void k_lif_bwd(const float4* __restrict__ g_z_
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) v += s_red[which][w][c];
     if (which == 0) {
       const float l = evf_sigmoid(leak[c]);
-      evf_atomic_add(g_leak + c, v * l * (1.0f - l));  // d sigmoid
+      if constexpr (DET) g_leak[(size_t)blockIdx.x * row_ld + c] += v * l * (1.0f - l);
+      else evf_atomic_add(g_leak + c, v * l * (1.0f - l));  // d sigmoid
     } else if (thresh[c] > 0.01f) {                     // clamp_min passes gradient only above the floor
-      evf_atomic_add(g_thresh + c, v);
+      if constexpr (DET) g_thresh[(size_t)blockIdx.x * row_ld + c] += v;
+      else evf_atomic_add(g_thresh + c, v);
     }
   }
 }
@@ -1126,9 +1131,27 @@ extern "C" int evf_lif_bwd(const float* g_z_out, const float* g_v_out, const flo
   const long npix = (long)B * H * W;
   // few, fat blocks: every block ends with 64 global atomics on the same 64 addresses
   const int nblk = (int)((npix * 8 + 255) / 256 < 768 ? (npix * 8 + 255) / 256 : 768);
-  hipLaunchKernelGGL(k_lif_bwd, dim3(nblk), dim3(256), 0, EVF_STREAM(stream), (const float4*)g_z_out,
+  hipLaunchKernelGGL(k_lif_bwd<false>, dim3(nblk), dim3(256), 0, EVF_STREAM(stream), (const float4*)g_z_out,
                      (const float4*)g_v_out, (const float4*)v_out, (const float4*)v_prev, z_prev, leak, thresh, npix,
-                     hard_reset, surrogate, act_width, (float4*)g_cur, (float4*)g_v_prev, g_leak, g_thresh);
+                     hard_reset, surrogate, act_width, (float4*)g_cur, (float4*)g_v_prev, g_leak, g_thresh, 0);
+  return evf_status();
+}
+
+// The fixed-order twin: per-block rows instead of the 64 atomics of every block (include/evflow.h).  The grid is the default
+// rule capped at the rows the caller has: a function of (B, H, W, nrows) alone.
+extern "C" int evf_lif_bwd_det(const float* g_z_out, const float* g_v_out, const float* v_out, const float* v_prev,
+                               const uint32_t* z_prev, const float* leak, const float* thresh, int B, int H, int W,
+                               int hard_reset, int surrogate, float act_width, float* g_cur, float* g_v_prev,
+                               float* g_leak, float* g_thresh, int row_ld, int nrows, void* stream) {
+  if (!v_out || !leak || !thresh || !g_cur || !g_v_prev || !g_leak || !g_thresh || B <= 0 || H <= 0 || W <= 0 ||
+      row_ld <= 0 || nrows <= 0)
+    return EVF_EINVAL;
+  const long npix = (long)B * H * W;
+  long nblk = (npix * 8 + 255) / 256 < 768 ? (npix * 8 + 255) / 256 : 768;
+  if (nblk > nrows) nblk = nrows;
+  hipLaunchKernelGGL(k_lif_bwd<true>, dim3((int)nblk), dim3(256), 0, EVF_STREAM(stream), (const float4*)g_z_out,
+                     (const float4*)g_v_out, (const float4*)v_out, (const float4*)v_prev, z_prev, leak, thresh, npix,
+                     hard_reset, surrogate, act_width, (float4*)g_cur, (float4*)g_v_prev, g_leak, g_thresh, row_ld);
   return evf_status();
 }
 
@@ -2036,9 +2059,12 @@ extern "C" int evf_conv_dgrad(const float* g_cur, const float* wT_a, float* g_a,
 // K = pixels.  Each wave walks whole image rows (grid-strided); the per-lane tap decode is
 // hoisted out of the pixel loop; the 4 waves of a block are summed through LDS stores and
 // the block adds its tile to dw (torch layout) with global atomics.
+// DET (evf_head_wgrad_det): dw is a [blocks][32 * Cin * 9] slab; block b stores its whole tile in row b (acc: adds to it
+// by plain read-modify-write) -- no atomic, and the slab need not be zero.  Everything up to the last loop is the same.
 #define HW_BLOCKS 256
+template <bool DET>
 __global__ __launch_bounds__(256) void k_head_wgrad(const float* __restrict__ x, const float* __restrict__ g, int B,
-                                                    int Cin, int H, int W, float* __restrict__ dw) {
+                                                    int Cin, int H, int W, float* __restrict__ dw, int acc_slab) {
   __shared__ float s_p[4][3 * C32 * C32];  // 48 KiB
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int i = lane & 31, h = lane >> 5;
@@ -2097,7 +2123,12 @@ __global__ __launch_bounds__(256) void k_head_wgrad(const float* __restrict__ x,
     const int co = e & 31, rr = e >> 5;
     if (rr < nrow) {
       const float v = (s_p[0][e] + s_p[1][e]) + (s_p[2][e] + s_p[3][e]);
-      evf_atomic_add(dw + (co * Cin + rr / 9) * 9 + rr % 9, v);
+      if constexpr (DET) {
+        float* d = dw + (size_t)blockIdx.x * (C32 * Cin * 9) + (co * Cin + rr / 9) * 9 + rr % 9;
+        *d = acc_slab ? *d + v : v;
+      } else {
+        evf_atomic_add(dw + (co * Cin + rr / 9) * 9 + rr % 9, v);
+      }
     }
   }
 }
@@ -2106,8 +2137,23 @@ extern "C" int evf_head_wgrad(const float* x, const float* g_cur, int B, int Cin
                               void* stream) {
   if (!x || !g_cur || !dw || B <= 0 || Cin <= 0 || Cin > HEAD_MAX_CIN || H <= 0 || W <= 0) return EVF_EINVAL;
   const long nb = ((long)B * H + 3) / 4;
-  hipLaunchKernelGGL(k_head_wgrad, dim3((int)(nb < HW_BLOCKS ? nb : HW_BLOCKS)), dim3(256), 0, EVF_STREAM(stream), x,
-                     g_cur, B, Cin, H, W, dw);
+  hipLaunchKernelGGL(k_head_wgrad<false>, dim3((int)(nb < HW_BLOCKS ? nb : HW_BLOCKS)), dim3(256), 0, EVF_STREAM(stream), x,
+                     g_cur, B, Cin, H, W, dw, 0);
+  return evf_status();
+}
+
+// The fixed-order twin: one slab row per block, the default's grid (a function of (B, H) alone)
+extern "C" int evf_head_wgrad_det_slabs(int B, int H, int W) {
+  (void)W;
+  if (B <= 0 || H <= 0) return 0;
+  const long nb = ((long)B * H + 3) / 4;
+  return (int)(nb < HW_BLOCKS ? nb : HW_BLOCKS);
+}
+extern "C" int evf_head_wgrad_det(const float* x, const float* g_cur, int B, int Cin, int H, int W, float* slab,
+                                  int accumulate, void* stream) {
+  if (!x || !g_cur || !slab || B <= 0 || Cin <= 0 || Cin > HEAD_MAX_CIN || H <= 0 || W <= 0) return EVF_EINVAL;
+  hipLaunchKernelGGL(k_head_wgrad<true>, dim3(evf_head_wgrad_det_slabs(B, H, W)), dim3(256), 0, EVF_STREAM(stream), x,
+                     g_cur, B, Cin, H, W, slab, accumulate & 1);
   return evf_status();
 }
 

@@ -112,6 +112,8 @@ class _Window:
         self.bwd_k = 0          # backward passes of this window so far
         self.lm = []            # PLIF_LAYER_MAJOR: (tape, dL/dflow, is_first) of the passes whose backward waits for the window's first
         self.slab_init = {}
+        self.head_det_rows = 0  # deterministic mode, head layer off the slab kernels: rows evf_lif_bwd_det may have written
+        self.det = False        # a pass of this window ran in deterministic mode (_FireNetPass.backward): _finalize adds in a fixed order
         self.token = eng._token(dev)  # (a leaf whose value is never read: only its autograd edge chains the passes)
         self.n_passes = 0
         # flow maps of the window's passes in ONE buffer [cap,B,2,H,W]: the loss reads them in place (no torch.stack)
@@ -138,6 +140,14 @@ class _FireNetPass(torch.autograd.Function):
     def backward(ctx, g_flow, g_token):
         eng, win = ctx.eng, ctx.win
         eng.flush_forward()
+        # the tail's mode, from the tape, for EVERY route a pass's backward can take below (layer-major window, top window, pass by
+        # pass): a window with one deterministic pass gets _finalize's fixed-order sums
+        win.det = win.det or bool(ctx.tape.get("det"))
+        if ctx.tape.get("det") and win.rows is None:
+            # (never the atomics instead: the rule of dataloader/encodings.py)
+            raise _lib.EvflowError("deterministic mode: the fused engine's backward needs the per-block parameter-gradient rows (precision "
+                                   "bf16x3, EVF_PARAM_ROWS=1); without them every per-channel gradient is summed with float atomics "
+                                   "(set_deterministic(False) / EVF_DETERMINISTIC=0 selects those)")
         if eng._lm_wanted(win, ctx.tape, g_flow):
             # layer-major backward of the window: nothing runs until the window's first pass has handed in its dL/dflow
             win.lm.append((ctx.tape, g_flow, ctx.is_first))
@@ -621,7 +631,8 @@ class FireNetEngine:
                       _lib.ptr(flow))
         if defer:
             self._defer_t += 1
-        tape = {"x_in": x_in, "layers": layers, "flow": flow} if record else None
+        # (det: the mode in force NOW also runs the backward -- a toggle in between cannot mix paths, loss/flow.py)
+        tape = {"x_in": x_in, "layers": layers, "flow": flow, "det": _lib.deterministic()} if record else None
         return flow, tape, new_states
 
     # ------------------------------------------------------------------ backward
@@ -863,12 +874,18 @@ class FireNetEngine:
         top_fused = (TOP_FUSED and g_flow is not None and self.precision == "bf16x3" and n > 1 and not self._al
                      and not self.cells[n - 1].recurrent and not win.gz_has[n - 1])  # (ALIF: evf_pred_bwd + the plain cell)
         g_flow_c = g_flow.float().contiguous() if g_flow is not None else None
+        # (win.det and the refusal of a window without per-block rows: _FireNetPass.backward, for every route)
         if self.__dict__.get("_bdefer_on", False):
             # recorded cells of this pass are launched later (flush_backward): its tape and the contiguous upstream gradient
             # must outlive this function (autograd drops ctx.tape and g_flow as soon as the node returns)
             self._bdefer_cur = (tape, g_flow, g_flow_c)
             self.__dict__.setdefault("_bdefer_keep", []).append(self._bdefer_cur)
         if g_flow is not None and not top_fused:
+            if tape.get("det"):
+                raise _lib.EvflowError("deterministic mode: the prediction head's backward outside the fused backward of the layer under it "
+                                       "(evf_pred_bwd) adds with float atomics; the fused form needs EVF_TOP_FUSED, precision bf16x3, a "
+                                       "feed-forward last layer and LIF / PLIF / XLIF cells (set_deterministic(False) / EVF_DETERMINISTIC=0 "
+                                       "selects the atomics; EVF_XLIF_FUSED=0 serves an ALIF network on the general path)")
             gz_top = win.buf(win.gz, n - 1)
             _lib.call("evf_pred_bwd", _lib.ptr(layers[n - 1][4]), _lib.ptr(tape["flow"]),
                       _lib.ptr(g_flow_c), _lib.ptr(self._flat["pred.w"]), B, H, W, _lib.ptr(gz_top),
@@ -1007,6 +1024,23 @@ class FireNetEngine:
                               self._act_width(0), _lib.ptr(win.g_cur) if plif else None, _lib.ptr(gv_out), _lib.ptr(leak_r),
                               _lib.ptr(thr_r), _lib.ptr(self._slabs[key]), (1 if win.slab_init.get(key) else 0) | (row_ld << 8))
                 win.slab_init[key] = True
+            elif i == 0 and tape.get("det"):
+                # deterministic mode, a head layer off the slab kernels (voxel input, Cin != 2): the fixed-order twins of the two calls
+                # below -- per-block rows and a per-block slab, added once per window by evf_grads_finalize
+                # (win.rows exists: checked at the top of the pass)
+                Cin = tape["x_in"].shape[1]
+                _lib.call("evf_lif_bwd_det", _lib.ptr(g_z), _lib.ptr(g_v), _lib.ptr(v_out), _lib.ptr(v_prev), _lib.ptr(z_prev),
+                          _lib.ptr(self._flat["0.leak"]), _lib.ptr(self._flat["0.thresh"]), B, H, W,
+                          1 if c.hard_reset else 0, SURROGATE_ID[c.activation], self._act_width(0), _lib.ptr(win.g_cur),
+                          _lib.ptr(gv_out), _lib.ptr(leak_r), _lib.ptr(thr_r), row_ld, win.rows.shape[0])
+                win.head_det_rows = win.rows.shape[0]
+                key = (0, "ff")
+                nsl = _lib.load().evf_head_wgrad_det_slabs(B, H, W)
+                if key not in self._slabs or self._slabs[key].shape != (nsl, C * Cin * 9) or self._slabs[key].device != dev:
+                    self._slabs[key] = _f32((nsl, C * Cin * 9), dev)
+                _lib.call("evf_head_wgrad_det", _lib.ptr(tape["x_in"]), _lib.ptr(win.g_cur), B, Cin, H, W,
+                          _lib.ptr(self._slabs[key]), 1 if win.slab_init.get(key) else 0)
+                win.slab_init[key] = True
             else:
                 _lib.call("evf_lif_bwd", _lib.ptr(g_z), _lib.ptr(g_v), _lib.ptr(v_out), _lib.ptr(v_prev), _lib.ptr(z_prev),
                           _lib.ptr(self._flat[f"{i}.leak"]), _lib.ptr(self._flat[f"{i}.thresh"]), B, H, W,
@@ -1120,7 +1154,9 @@ class FireNetEngine:
                 # (the head layer's TRACE parameters can also be written by the stand-alone evf_plif_trace_bwd -- EVF_PLIF_TRACE_FUSED=0,
                 # or a head cell the fused window kernel does not serve -- with up to 512 rows whatever the head launch's block count)
                 trace_par = name.endswith(("leak_pt", "add_pt"))
-                seg_rows.append((max(rows_head, 512) if trace_par else rows_head) if name.startswith("0.") else rows_hidden)
+                # (deterministic mode, voxel input: evf_lif_bwd_det writes up to win.head_det_rows rows of the head's leak / thresh)
+                rows_h = max(rows_head, win.head_det_rows)
+                seg_rows.append((max(rows_h, 512) if trace_par else rows_h) if name.startswith("0.") else rows_hidden)
             else:
                 i, nm = name.split(".")
                 if win.slab_init.get((int(i), nm)):
@@ -1157,8 +1193,24 @@ class FireNetEngine:
                  else _lib.load().evf_conv_wgrad_slabs(B, H, W))
         if FUSED_TAIL and self._finalize_fused(win, nslab):
             return [None] * len(self.params)
+        # deterministic mode: evf_sum_rows in its ACCUMULATING form adds 128 rows and more with float atomics (k_sum_rows_acc), and
+        # evf_reduce_slabs adds its eight slab groups atomically -- the step-by-step tail then sums into a temporary with the
+        # fixed-order forms (k_sum_rows, k_reduce_wgrad_multi) and adds that element-wise
+        det = win.det
+
+        def sum_rows(buf, dst, clear):
+            if det:
+                # (one persistent scratch per engine, like the slabs: small_size floats hold the rows' width and the head slab's)
+                if self.__dict__.get("_tail_tmp") is None or self._tail_tmp.device != win.dev:
+                    self._tail_tmp = _f32((self.small_size,), win.dev)
+                tmp = self._tail_tmp[:buf.shape[1]]
+                _lib.call("evf_sum_rows", _lib.ptr(buf), buf.shape[0], buf.shape[1], 2 if clear else 0, _lib.ptr(tmp))
+                dst.add_(tmp)
+            else:
+                _lib.call("evf_sum_rows", _lib.ptr(buf), buf.shape[0], buf.shape[1], 1 | (2 if clear else 0), _lib.ptr(dst))
+
         if win.rows is not None:  # per-block partials of the per-channel gradients -> the small accumulator (rows zeroed)
-            _lib.call("evf_sum_rows", _lib.ptr(win.rows), win.rows.shape[0], win.rows.shape[1], 1 | 2, _lib.ptr(win.small))
+            sum_rows(win.rows, win.small, True)
             self._rows_clean = True
         grads = []
         seg_src, seg_dst, seg_n = [], [], []
@@ -1172,8 +1224,7 @@ class FireNetEngine:
             direct = hip_ops.DIRECT_PARAM_GRADS and p.grad is not None and p.grad.dtype == torch.float32 and p.grad.is_contiguous() and p.grad.is_cuda
             if name in self.small_off:
                 if name == "0.ff" and win.slab_init.get((0, "ff")):  # head weight gradient: per-block partials
-                    sl = self._slabs[(0, "ff")]
-                    _lib.call("evf_sum_rows", _lib.ptr(sl), sl.shape[0], sl.shape[1], 1, _lib.ptr(self._small(win, name)))
+                    sum_rows(self._slabs[(0, "ff")], self._small(win, name), False)
                 if direct:
                     seg_src.append(self.small_off[name][0])
                     seg_dst.append(p.grad)
@@ -1191,7 +1242,10 @@ class FireNetEngine:
                 grads.append(None)
                 continue
             g = _lib.zeros(p.shape, dtype=torch.float32, device=win.dev)
-            if win.slab_init.get(k):
+            if win.slab_init.get(k) and det:  # (g is zero: the accumulating multi form, one tensor, sums in a fixed order)
+                _lib.call("evf_reduce_slabs_multi", (ctypes.c_void_p * 1)(self._slabs[k].data_ptr()), (ctypes.c_void_p * 1)(g.data_ptr()), 1,
+                          nslab, 9 * C * C)
+            elif win.slab_init.get(k):
                 _lib.call("evf_reduce_slabs", _lib.ptr(self._slabs[k]), nslab, 9 * C * C, 0, _lib.ptr(g))
             grads.append(g.to(p.dtype))
         for lo in range(0, len(red_src), 16):  # all conv-weight slabs in one launch (16 tensors per call)

@@ -366,6 +366,11 @@ def norm_nonzero(x):
     _lib.require_gpu(x, "norm_input")
     xc = x.detach().float().contiguous()
     out = torch.empty_like(xc)
+    if _lib.deterministic():  # per-block partial sums added in a fixed order (the scratch need not be zero)
+        nws = _lib.load().evf_norm_nonzero_det_ws(xc.numel())
+        ws = torch.empty(nws, dtype=torch.float64, device=xc.device)
+        _lib.call("evf_norm_nonzero_det", _lib.ptr(xc), xc.numel(), _lib.ptr(out), ws.data_ptr(), nws)
+        return out
     ws = torch.empty(3, dtype=torch.float64, device=xc.device)
     _lib.call("evf_norm_nonzero", _lib.ptr(xc), xc.numel(), _lib.ptr(out), ws.data_ptr())
     return out

@@ -340,6 +340,17 @@ int evf_lif_bwd(const float* g_z_out, const float* g_v_out, const float* v_out,
                 const float* leak, const float* thresh, int B, int H, int W,
                 int hard_reset, int surrogate, float act_width,
                 float* g_cur, float* g_v_prev, float* g_leak, float* g_thresh, void* stream);
+/* evf_lif_bwd with reproducible per-channel sums (autograd of spiking_submodules.py:103-126 / :523-551, the leak through its
+ * sigmoid and the threshold through clamp_min(0.01)): g_leak / g_thresh address ROW 0 of a [nrows][row_ld] buffer of per-block
+ * partial sums (the convention of evf_lif_bwd_wgrad*, see evf_sum_rows) and block b ADDS its 32 + 32 channel sums to row b by
+ * plain read-modify-write -- no atomic.  The grid is min(evf_lif_bwd's rule, nrows), a function of (B, H, W, nrows) alone; rows
+ * behind it are not touched.  g_cur / g_v_prev are evf_lif_bwd's.  EVF_EINVAL for what evf_lif_bwd refuses and for
+ * row_ld <= 0 or nrows <= 0, before any launch. */
+int evf_lif_bwd_det(const float* g_z_out, const float* g_v_out, const float* v_out,
+                    const float* v_prev, const uint32_t* z_prev,
+                    const float* leak, const float* thresh, int B, int H, int W,
+                    int hard_reset, int surrogate, float act_width,
+                    float* g_cur, float* g_v_prev, float* g_leak, float* g_thresh, int row_ld, int nrows, void* stream);
 
 /* Fused neuron backward + weight gradients of one 32->32 cell (layers fed by spikes):
  * evf_lif_bwd and evf_conv_wgrad_bits (for the ff input and, when zT_prev != NULL, the
@@ -618,11 +629,28 @@ int evf_add_segments(float* src, void* const* dst, const int* off, const int* n,
 int evf_sum_rows(float* rows, int nrows, int n, int accumulate, float* dst, void* stream);
 /* Head weight gradient: dW[co][ci][ky][kx] += sum g_cur[pix][co]*x[b][ci][pix+tap] (torch layout out). */
 int evf_head_wgrad(const float* x, const float* g_cur, int B, int Cin, int H, int W, float* dw, void* stream);
+/* evf_head_wgrad with a reproducible sum (the weight gradient of the head convolution, models/submodules.py:52-61 under
+ * models/model.py:120-125 with any num_bins): slab [evf_head_wgrad_det_slabs(B,H,W)][32*Cin*9], every row in the torch layout
+ * [32][Cin][3][3].  Block b owns row b: accumulate = 0 stores its whole tile, zeros included (the slab need not be zero),
+ * accumulate = 1 adds to the row by plain read-modify-write -- no atomic.  The grid, min(ceil(B*H/4), 256), is a function of
+ * (B, H) alone.  The rows are added once per window by evf_grads_finalize (head_rows) or evf_sum_rows (accumulate = 0).
+ * EVF_EINVAL for what evf_head_wgrad refuses (Cin outside 1..8) and for a null slab, before any launch. */
+int evf_head_wgrad_det_slabs(int B, int H, int W);
+int evf_head_wgrad_det(const float* x, const float* g_cur, int B, int Cin, int H, int W, float* slab, int accumulate,
+                       void* stream);
 
 /* norm_input of every model's forward (models/model.py:247-252): out = x with its NON-ZERO entries replaced by
  * (x - mean) / std, mean and unbiased std taken over the non-zero entries of the whole tensor.  ws3: 3 doubles of
  * scratch.  out may alias x. */
 int evf_norm_nonzero(const float* x, int64_t n, float* out, double* ws3, void* stream);
+/* evf_norm_nonzero with reproducible statistics (models/model.py:247-252): three launches on the same grid,
+ * min(ceil(n/1024), 1024) blocks -- a function of n alone.  ws [>= evf_norm_nonzero_det_ws(n) doubles; need not be zero] holds
+ * one (sum, count) and one sum of squared deviations per block, stored by the block; the blocks of the next launch each add all
+ * of them in one fixed order, so all hold the same mean and std.  No memset, no atomic, no block waits for another.  Zero
+ * entries (-0.0 included) stay 0.f; one non-zero entry gives NaN there, as torch.std does; none leaves all zeros.  out may alias
+ * x.  EVF_EINVAL for a null or short ws, before any launch. */
+int64_t evf_norm_nonzero_det_ws(int64_t n);
+int evf_norm_nonzero_det(const float* x, int64_t n, float* out, double* ws, int64_t ws_doubles, void* stream);
 
 /* Prediction head: 1x1 conv 32->2 + bias + tanh (models/submodules.py:52-61,
  * model.py:197-199) on bit-packed spikes -> flow [B,2,H,W] (NCHW). */
