@@ -156,6 +156,21 @@ __device__ __forceinline__ void evf_put(float* __restrict__ img, long px, float 
   if (img && v != 0.f) evf_atomic_add(img + px, v);
 }
 
+// THE bilinear taps of every splat of this file: the 2 x 2 corners of a warped position and their weights, corner (cy[j], cx[i])
+// weighs ay[j] * ax[i].  The library builds with -ffp-contract=off, so every user gets the same bits from these expressions.
+struct Taps {
+  float cy[2], cx[2], ay[2], ax[2];
+};
+__device__ __forceinline__ Taps evf_taps(float wy, float wx) {
+  Taps t = {{floorf(wy), floorf(wy + 1.0f)}, {floorf(wx), floorf(wx + 1.0f)}, {}, {}};
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    t.ay[k] = fmaxf(0.f, 1.0f - fabsf(wy - t.cy[k]));
+    t.ax[k] = fmaxf(0.f, 1.0f - fabsf(wx - t.cx[k]));
+  }
+  return t;
+}
+
 template <bool ROUND>
 __device__ __forceinline__ void evf_splat(const Warp w, int H, int W, float a0, float a1, float tau, float* I0,
                                           float* I1, float* T0, float* T1) {
@@ -168,22 +183,15 @@ __device__ __forceinline__ void evf_splat(const Warp w, int H, int W, float a0, 
     evf_put(T0, px, tau * a0);
     evf_put(T1, px, tau * a1);
   } else {
-    const float cy[2] = {floorf(w.wy), floorf(w.wy + 1.0f)};
-    const float cx[2] = {floorf(w.wx), floorf(w.wx + 1.0f)};
-    float ay[2], ax[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      ay[k] = fmaxf(0.f, 1.0f - fabsf(w.wy - cy[k]));
-      ax[k] = fmaxf(0.f, 1.0f - fabsf(w.wx - cx[k]));
-    }
+    const Taps c = evf_taps(w.wy, w.wx);
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        if (cy[j] < 0.f || cy[j] >= (float)H || cx[i] < 0.f || cx[i] >= (float)W) continue;
-        const float wt = ay[j] * ax[i];
+        if (c.cy[j] < 0.f || c.cy[j] >= (float)H || c.cx[i] < 0.f || c.cx[i] >= (float)W) continue;
+        const float wt = c.ay[j] * c.ax[i];
         if (wt == 0.f) continue;
-        const long px = (long)(cy[j] * (float)W + cx[i]);
+        const long px = (long)(c.cy[j] * (float)W + c.cx[i]);
         evf_put(I0, px, wt * a0);
         evf_put(I1, px, wt * a1);
         const float wtau = wt * tau;  // (fw_weights * ts_list) * polarity_mask, loss/flow.py:206-211
@@ -233,12 +241,175 @@ __global__ void k_iwe_splat(const float* __restrict__ flow, const float4* __rest
   evf_splat<ROUND>(evf_warp(t, q.y, q.z, fy, fx, tref, S), H, W, a0, a1, tau, I0, I1, T0, T1);
 }
 
-// LDS-privatised variant: one block owns a stripe of `rows` image rows of ONE sample (all
-// nch channels) in LDS, scans every event of that sample, keeps the taps that land in its
-// stripe with LDS atomics and finally writes the stripe with coalesced float4 stores.
-// Device-scope fp32 atomics on global memory top out near 21 G atomics/s on MI355X (they
-// are resolved at the memory side of the 8 non-coherent L2s); LDS atomics scale with the
-// CUs.  Same arithmetic as k_iwe_splat (integer histograms stay bit-exact).
+// ---- stripe kernels: a block owns a stripe of image rows in LDS, in one of two forms --------------------------------------
+// What differs between the default (float) and the deterministic (exact-sum) stripe kernels is how a term is accumulated, and
+// nothing else: the slot type, its zero, add and get.  Every per-event term comes from ONE body instantiated with either policy.
+struct AccFloat {  // fp32 slots, LDS float atomics: the sum depends on the order in which the lanes deliver its terms
+  typedef float slot;
+  static constexpr bool exact = false;
+  static constexpr slot zero = 0.f;
+  __device__ __forceinline__ void add(slot* p, float v) const {
+#ifdef CM_PROBE_NOATOM  // (probe build: plain stores instead of the float atomics -- wrong sums, valid timing)
+    *p = v;
+#else
+    atomicAdd(p, v);
+#endif
+  }
+  __device__ __forceinline__ float get(const slot* p) const { return *p; }
+};
+struct AccFixed {  // two's complement 64-bit slots: the term scaled by 2^k2 (ldexpf: exact), rounded ONCE, added as an integer --
+  typedef unsigned long long slot;  // integer addition is associative, the sum is a function of the SET of its terms
+  static constexpr bool exact = true;
+  static constexpr slot zero = 0ull;
+  int k2;
+  __device__ __forceinline__ void add(slot* p, float v) const { atomicAdd(p, (slot)__float2ll_rn(ldexpf(v, k2))); }
+  __device__ __forceinline__ float get(const slot* p) const { return ldexpf(__ll2float_rn((long long)*p), -k2); }
+};
+
+struct Stripe {  // image rows r0 .. r0 + nr are block blockIdx.x's; an LDS plane of the stripe holds `plane` slots
+  int r0, nr, plane;
+};
+template <class A>
+__device__ __forceinline__ Stripe stripe_begin(typename A::slot* img, int nplanes, int rows, int H, int W) {  // -> all slots zero
+  const int r0 = blockIdx.x * rows;
+  const Stripe s = {r0, min(rows, H - r0), rows * W};
+  for (int q = threadIdx.x; q < nplanes * s.plane; q += blockDim.x) img[q] = A::zero;
+  __syncthreads();
+  return s;
+}
+// the stripe's sums -> floats, every sum converted ONCE: planes [nplanes][H*W] of one sample at `o`, n = nr * W values each
+template <class A>
+__device__ __forceinline__ void stripe_out(const A acc, const typename A::slot* __restrict__ img, int nplanes, int plane, int n,
+                                           float* __restrict__ o, long HW) {
+  for (int c = 0; c < nplanes; ++c)
+    for (int q = threadIdx.x; q < n; q += blockDim.x) o[c * HW + q] = acc.get(img + c * plane + q);
+}
+
+// The IWE stripe body (k_iwe_splat_lds, k_iwe_splat_det): one block owns a stripe of `rows` image rows of ONE sample (all nch
+// channels) in LDS, scans every event of that sample, keeps the taps that land in its stripe with LDS atomics and finally writes
+// the stripe with coalesced stores.  Device-scope fp32 atomics on global memory top out near 21 G atomics/s on MI355X (they are
+// resolved at the memory side of the 8 non-coherent L2s); LDS atomics scale with the CUs.  Per event the flow gather, `flow * 0`,
+// the warp, the taps and the products of k_iwe_splat.  The exact form differs in three places, each marked below:
+//   * it skips an event whose own pixel lies outside the flow map (the float form reads out of bounds there) and taps with
+//     non-finite coordinates (the float form lets NaN into the image: non-finite flow is outside the deterministic contract);
+//   * it tests the stripe BEFORE the taps (the float form inside `put`) ...
+//   * ... and loads the weights behind that test (the float form up front, an adjacent pair in one 8-byte load).
+template <bool ROUND, class A>
+__device__ __forceinline__ void iwe_stripe_body(const A acc, const float* __restrict__ flow, const float4* __restrict__ ev,
+                                                const int32_t* __restrict__ map_of_event, const int32_t* __restrict__ ts_shift,
+                                                const float* __restrict__ w0, const float* __restrict__ w1, int wstride, int B,
+                                                int M, int H, int W, float S, float tref, float tref_ts, int mode, int nch,
+                                                int rows, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  typename A::slot* img = (typename A::slot*)smem_raw;  // [nch][rows][W]
+  const int b = blockIdx.y;
+  const Stripe s = stripe_begin<A>(img, nch, rows, H, W);
+  const long HW = (long)H * W;
+  const float lo = (float)s.r0, hi = (float)(s.r0 + s.nr), fW = (float)W;
+  auto in_stripe = [&](float cy) { return cy >= lo && cy < hi; };
+  auto inside = [&](float cy, float cx) {  // this tap is kept (the float form: in the image, `put` tests the stripe)
+    if (A::exact) return in_stripe(cy) && cx >= 0.f && cx < fW;  // (NaN: no)
+    return !(cy < 0.f || cy >= (float)H || cx < 0.f || cx >= (float)W);
+  };
+  auto slot_of = [&](float cy, float cx) { return ((int)cy - s.r0) * W + (int)cx; };  // (index in a plane)
+  // exact form: px is the tap's slot, found once behind the stripe test; float form: stripe test and slot per plane, here
+  auto put = [&](int px, int ch, float cy, float cx, float v) {
+    if (v != 0.f && (A::exact || in_stripe(cy))) acc.add(&img[ch * s.plane + (A::exact ? px : slot_of(cy, cx))], v);
+  };
+  // the two weights as adjacent floats (the reference's [B,N,2] polarity mask): one 8-byte load
+  const bool pair = !A::exact && w0 && w1 == w0 + 1 && wstride == 2 && (((uintptr_t)w0) & 7) == 0;
+  auto weights = [&](long i, float& a0, float& a1) {
+    if (pair) {
+      const float2 a = *(const float2*)(w0 + i * 2);
+      a0 = a.x, a1 = a.y;
+    } else {
+      a0 = w0 ? w0[i * wstride] : 1.0f;
+      a1 = w1 ? w1[i * wstride] : 0.0f;
+    }
+  };
+  // events in batches of U per thread: all event loads first, then all flow gathers (which depend on them), then the splats --
+  // the two dependent memory latencies are paid once per batch
+  constexpr int U = 4;
+  for (int e0 = threadIdx.x; e0 < M; e0 += U * blockDim.x) {
+    float4 qs[U];
+    float a0s[U], a1s[U], ts[U], fys[U], fxs[U];
+    int maps[U];
+    long is[U];
+    bool ok[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int e = min(e0 + u * (int)blockDim.x, M - 1);  // clamped: loads stay unconditional
+      is[u] = (long)b * M + e;
+      qs[u] = ev[is[u]];
+      ts[u] = ts_shift ? (float)ts_shift[e] : 0.f;
+      maps[u] = map_of_event ? map_of_event[e] : 0;
+      if (A::exact) a0s[u] = a1s[u] = 0.f;  // (loaded behind the stripe test)
+      else weights(is[u], a0s[u], a1s[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      ok[u] = e0 + u * (int)blockDim.x < M;
+      if (A::exact) {  // the index of evf_event_flow, checked before it is used
+        const float lin = qs[u].y * fW + qs[u].z;
+        ok[u] = ok[u] && lin > -1.0f && lin < (float)HW;
+      }
+      fys[u] = fxs[u] = 0.f;
+      if (!A::exact || ok[u]) evf_event_flow(flow, maps[u], B, b, HW, qs[u].y, qs[u].z, W, fys[u], fxs[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (!ok[u]) continue;
+      const float4 q = qs[u];
+      const float t = q.x + ts[u];
+      float fy = fys[u], fx = fxs[u];
+      float &a0 = a0s[u], &a1 = a1s[u];
+      if (mode & 2) {  // `flow * 0` keeps the sign/NaN semantics of the reference
+        fy *= 0.f;
+        fx *= 0.f;
+      }
+      const float tau = (mode & 8) ? (tref_ts - t) : t;
+      const Warp w = evf_warp(t, q.y, q.z, fy, fx, tref, S);
+      if (ROUND) {
+        const float iy = rintf(w.wy), ix = rintf(w.wx);
+        if (!inside(iy, ix)) continue;
+        if (A::exact) weights(is[u], a0, a1);
+        const int px = A::exact ? slot_of(iy, ix) : 0;
+        put(px, 0, iy, ix, a0);
+        if (nch >= 2) put(px, 1, iy, ix, a1);
+        if (nch == 4) {
+          put(px, 2, iy, ix, tau * a0);
+          put(px, 3, iy, ix, tau * a1);
+        }
+      } else {
+        const Taps c = evf_taps(w.wy, w.wx);
+        if (A::exact) {
+          if (!(in_stripe(c.cy[0]) || in_stripe(c.cy[1]))) continue;
+          weights(is[u], a0, a1);
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            if (!inside(c.cy[j], c.cx[k])) continue;
+            const float wt = c.ay[j] * c.ax[k];
+            if (wt == 0.f) continue;
+            const int px = A::exact ? slot_of(c.cy[j], c.cx[k]) : 0;
+            put(px, 0, c.cy[j], c.cx[k], wt * a0);
+            if (nch >= 2) put(px, 1, c.cy[j], c.cx[k], wt * a1);
+            if (nch == 4) {
+              const float wtau = wt * tau;
+              put(px, 2, c.cy[j], c.cx[k], wtau * a0);
+              put(px, 3, c.cy[j], c.cx[k], wtau * a1);
+            }
+          }
+      }
+    }
+  }
+  __syncthreads();
+  stripe_out(acc, img, nch, s.plane, s.nr * W, out + (long)b * nch * HW + (long)s.r0 * W, HW);
+}
+
+// the float form: same arithmetic as k_iwe_splat (integer histograms stay bit-exact)
 template <bool ROUND>
 __global__ __launch_bounds__(1024) void k_iwe_splat_lds(const float* __restrict__ flow, const float4* __restrict__ ev,
                                                         const int32_t* __restrict__ map_of_event,
@@ -247,92 +418,8 @@ __global__ __launch_bounds__(1024) void k_iwe_splat_lds(const float* __restrict_
                                                         int wstride, int B, int M, int H, int W, float S, float tref,
                                                         float tref_ts, int mode, int nch, int rows,
                                                         float* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* img = (float*)smem_raw;  // [nch][rows][W]
-  const int b = blockIdx.y, r0 = blockIdx.x * rows;
-  const int nr = min(rows, H - r0);
-  const int plane = rows * W;
-  for (int q = threadIdx.x; q < nch * plane; q += blockDim.x) img[q] = 0.f;
-  __syncthreads();
-  const long HW = (long)H * W;
-  const float lo = (float)r0, hi = (float)(r0 + nr);
-  auto put = [&](int ch, float cy, float cx, float v) {
-    if (v != 0.f && cy >= lo && cy < hi) atomicAdd(&img[ch * plane + ((int)cy - r0) * W + (int)cx], v);
-  };
-  // events in batches of IW_U per thread: all event loads first, then all flow gathers (which
-  // depend on them), then the splats -- the two dependent memory latencies are paid once per batch
-#define IW_U 4
-  const bool pair = w0 && w1 == w0 + 1 && wstride == 2 && (((uintptr_t)w0) & 7) == 0;
-  for (int e0 = threadIdx.x; e0 < M; e0 += IW_U * blockDim.x) {
-    float4 qs[IW_U];
-    float a0s[IW_U], a1s[IW_U], ts[IW_U], fys[IW_U], fxs[IW_U];
-    int maps[IW_U];
-#pragma unroll
-    for (int u = 0; u < IW_U; ++u) {
-      const int e = min(e0 + u * (int)blockDim.x, M - 1);  // clamped: loads stay unconditional
-      const long i = (long)b * M + e;
-      qs[u] = ev[i];
-      ts[u] = ts_shift ? (float)ts_shift[e] : 0.f;
-      maps[u] = map_of_event ? map_of_event[e] : 0;
-      if (pair) {  // the two weights are adjacent floats (the reference's [B,N,2] polarity mask): one 8-byte load
-        const float2 a = *(const float2*)(w0 + i * 2);
-        a0s[u] = a.x, a1s[u] = a.y;
-      } else {
-        a0s[u] = w0 ? w0[i * wstride] : 1.0f;
-        a1s[u] = w1 ? w1[i * wstride] : 0.0f;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < IW_U; ++u) evf_event_flow(flow, maps[u], B, b, HW, qs[u].y, qs[u].z, W, fys[u], fxs[u]);
-#pragma unroll
-    for (int u = 0; u < IW_U; ++u) {
-    if (e0 + u * (int)blockDim.x >= M) continue;
-    const float4 q = qs[u];
-    const float t = q.x + ts[u];
-    float fy = fys[u], fx = fxs[u];
-    const float a0 = a0s[u], a1 = a1s[u];
-    if (mode & 2) {
-      fy *= 0.f;
-      fx *= 0.f;
-    }
-    const float tau = (mode & 8) ? (tref_ts - t) : t;
-    const Warp w = evf_warp(t, q.y, q.z, fy, fx, tref, S);
-    if (ROUND) {
-      const float iy = rintf(w.wy), ix = rintf(w.wx);
-      if (iy < 0.f || iy >= (float)H || ix < 0.f || ix >= (float)W) continue;
-      put(0, iy, ix, a0);
-      if (nch >= 2) put(1, iy, ix, a1);
-      if (nch == 4) {
-        put(2, iy, ix, tau * a0);
-        put(3, iy, ix, tau * a1);
-      }
-    } else {
-      const float cy[2] = {floorf(w.wy), floorf(w.wy + 1.0f)};
-      const float cx[2] = {floorf(w.wx), floorf(w.wx + 1.0f)};
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          if (cy[j] < 0.f || cy[j] >= (float)H || cx[k] < 0.f || cx[k] >= (float)W) continue;
-          const float wt = fmaxf(0.f, 1.0f - fabsf(w.wy - cy[j])) * fmaxf(0.f, 1.0f - fabsf(w.wx - cx[k]));
-          if (wt == 0.f) continue;
-          put(0, cy[j], cx[k], wt * a0);
-          if (nch >= 2) put(1, cy[j], cx[k], wt * a1);
-          if (nch == 4) {
-            const float wtau = wt * tau;
-            put(2, cy[j], cx[k], wtau * a0);
-            put(3, cy[j], cx[k], wtau * a1);
-          }
-        }
-    }
-    }
-  }
-#undef IW_U
-  __syncthreads();
-  for (int ch = 0; ch < nch; ++ch) {
-    float* dst = out + ((long)b * nch + ch) * HW + (long)r0 * W;
-    for (int q = threadIdx.x; q < nr * W; q += blockDim.x) dst[q] = img[ch * plane + q];
-  }
+  iwe_stripe_body<ROUND>(AccFloat{}, flow, ev, map_of_event, ts_shift, w0, w1, wstride, B, M, H, W, S, tref, tref_ts, mode, nch,
+                         rows, out);
 }
 
 // Single flow map, one image plane <= 64 KiB, M <= 16 Ki events per sample (compute_pol_iwe at the
@@ -586,6 +673,18 @@ __global__ __launch_bounds__(1024) void k_iwe_splat_one(const float* __restrict_
   if (tid == 0) __hip_atomic_store(ticket + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// THE stripe-height rule of every stripe kernel: as many rows as `slots` LDS slots hold of `planes` planes of width W, at most H,
+// halved while above 8 and the grid -- `samples` rows of blocks x the stripes -- is short of `target` blocks (every block re-reads
+// its sample's events, L2 resident: shorter stripes trade redundant event reads for parallelism).  0: not one row fits.
+static int stripe_rows(int slots, int planes, long samples, int H, int W, int target, bool round_up = false) {
+  int rows = slots / (planes * W);
+  if (rows > H) rows = H;
+  while (rows > 8 && samples * evf_cdiv(H, rows) < target) rows = (rows + (round_up ? 1 : 0)) / 2;
+  return rows;
+}
+#define STRIPE_FLOATS 32768     // what a stripe may take of the CU's LDS, 128 KiB: fp32 slots (AccFloat) ...
+#define SPLAT_DET_SLOTS 16384  // ... and 64-bit slots (AccFixed)
+
 extern "C" int evf_iwe_splat(const float* flow, const float* ev, const int32_t* map_of_event, const int32_t* ts_shift,
                              const float* w0, const float* w1, int wstride, int B, int M, int H, int W,
                              float flow_scaling, float tref, float tref_ts, int mode, int nch, float* out, void* stream) {
@@ -594,9 +693,6 @@ extern "C" int evf_iwe_splat(const float* flow, const float* ev, const int32_t* 
   if (M > 0 && !ev) return EVF_EINVAL;
   hipStream_t st = EVF_STREAM(stream);
   if (M == 0) return evf_hip(evf_memset_async(out, 0, sizeof(float) * (size_t)B * nch * H * W, st));
-  // stripe height: as tall as 128 KiB of LDS allows, shrunk (down to 8 rows) until the grid has
-  // >= 256 blocks; every block re-reads the sample's events (L2 resident), so shorter stripes
-  // trade redundant event reads for parallelism
   // register-resident events + one reused LDS plane: single flow map, plane <= 64 KiB, M <= 16 Ki events,
   // enough samples to fill the CUs
   // Register-resident events + one reused LDS plane (k_iwe_splat_reg): rounded indices, single flow map, no
@@ -626,7 +722,6 @@ extern "C" int evf_iwe_splat(const float* flow, const float* ev, const int32_t* 
       return evf_status();
     }
   }
-  const int max_rows = (128 * 1024) / (nch * W * 4);
   // small problems (a few 100k events) are latency bound: there the one-launch kernel below (one entry per event, the image
   // built in LDS by the sample's last block) or, for shapes it does not serve, the plain global-atomic kernel behind a
   // zero-fill; the LDS stripe version wins once the device-scope atomics saturate
@@ -662,9 +757,8 @@ extern "C" int evf_iwe_splat(const float* flow, const float* ev, const int32_t* 
       return evf_status();
     }
   }
-  if (max_rows >= 1 && (long)B * M >= lds_min) {
-    int rows = max_rows < H ? max_rows : H;
-    while (rows > 8 && (long)B * evf_cdiv(H, rows) < 256) rows = (rows + 1) / 2;
+  const int rows = stripe_rows(STRIPE_FLOATS, nch, B, H, W, 256, true);  // (256 blocks, halving rounds up)
+  if (rows >= 1 && (long)B * M >= lds_min) {
     const size_t lds = (size_t)nch * rows * W * 4;
     static bool attr[2] = {false, false};
     const int r = (mode & 1) ? 1 : 0;
@@ -841,49 +935,36 @@ struct CmFin {  // what the LAST block of k_cm_splat_lds needs to finish the los
 __device__ void cm_finalize_body(float* red, const float* stats, const float* __restrict__ part, int S, int B, int Pm,
                                  int nblk_per_scale, float weight, int comps, int loss_scaling, float* __restrict__ loss);
 
-__global__ __launch_bounds__(1024) void k_cm_splat_lds(const float4* __restrict__ warp, const float* __restrict__ tabs,
-                                                       const float* __restrict__ ys, int B, int M, int H, int W, int rows, float P,
-                                                       float* __restrict__ images, CmFin fin) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* img = (float*)smem_raw;  // [4][rows*W]: I_pos, I_neg, TS_pos, TS_neg of this direction
+// The CM stripe body (k_cm_splat_lds, k_cm_splat_det): block (stripe, sbd = (scale * B + sample) * 2 + direction) zeroes its
+// stripe of the four images of that direction in LDS -- img [4][rows*W]: I_pos, I_neg, TS_pos, TS_neg --, scans the sample's
+// pre-warped events and accumulates the taps of its own through the policy.  Returns behind the barrier that ends the scan.
+template <class A>
+__device__ __forceinline__ Stripe cm_stripe_body(const A acc, typename A::slot* img, const float4* __restrict__ warp,
+                                                 const float* __restrict__ tabs, const float* __restrict__ ys, int B, int M, int H,
+                                                 int W, int rows, float P) {
   const int sbd = blockIdx.y, d = sbd & 1, b = (sbd >> 1) % B;
-  const int r0 = blockIdx.x * rows, nr = min(rows, H - r0), plane = rows * W;
-  for (int q = threadIdx.x; q < 4 * plane; q += blockDim.x) img[q] = 0.f;
-  __syncthreads();
+  const Stripe s = stripe_begin<A>(img, 4, rows, H, W);
+  const int plane = s.plane;
   const float4* __restrict__ wp = warp + (long)sbd * M;
   const float* __restrict__ tb = tabs + (long)b * M;
-  const float lo = (float)r0, hi = (float)(r0 + nr), fW = (float)W;
+  const float lo = (float)s.r0, hi = (float)(s.r0 + s.nr), fW = (float)W;
   auto one = [&](const float4 w4, const float t) {
     const float tau = d ? P - t : t;  // timestamp images: t forward, (P - t) backward (loss/flow.py:196-211, 229-244)
-    const float cy[2] = {floorf(w4.x), floorf(w4.x + 1.0f)};
-    const float cx[2] = {floorf(w4.y), floorf(w4.y + 1.0f)};
-    float ay[2], ax[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      ay[k] = fmaxf(0.f, 1.0f - fabsf(w4.x - cy[k]));
-      ax[k] = fmaxf(0.f, 1.0f - fabsf(w4.y - cx[k]));
-    }
+    const Taps c = evf_taps(w4.x, w4.y);
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        if (!(cy[j] >= lo && cy[j] < hi && cx[i] >= 0.f && cx[i] < fW)) continue;  // other stripes / outside (NaN too)
-        const float wt = ay[j] * ax[i];
+        if (!(c.cy[j] >= lo && c.cy[j] < hi && c.cx[i] >= 0.f && c.cx[i] < fW)) continue;  // other stripes / outside (NaN too)
+        const float wt = c.ay[j] * c.ax[i];
         if (wt == 0.f) continue;
-        float* px = img + ((int)cy[j] - r0) * W + (int)cx[i];
+        typename A::slot* px = img + ((int)c.cy[j] - s.r0) * W + (int)c.cx[i];
         const float wtau = wt * tau;
         const float v0 = wt * w4.z, v1 = wt * w4.w, u0 = wtau * w4.z, u1 = wtau * w4.w;
-#ifdef CM_PROBE_NOATOM  // (probe build: plain stores instead of the float atomics -- wrong sums, valid timing)
-        if (v0 != 0.f) px[0] = v0;
-        if (v1 != 0.f) px[plane] = v1;
-        if (u0 != 0.f) px[2 * plane] = u0;
-        if (u1 != 0.f) px[3 * plane] = u1;
-#else
-        if (v0 != 0.f) atomicAdd(px, v0);
-        if (v1 != 0.f) atomicAdd(px + plane, v1);
-        if (u0 != 0.f) atomicAdd(px + 2 * plane, u0);
-        if (u1 != 0.f) atomicAdd(px + 3 * plane, u1);
-#endif
+        if (v0 != 0.f) acc.add(px, v0);
+        if (v1 != 0.f) acc.add(px + plane, v1);
+        if (u0 != 0.f) acc.add(px + 2 * plane, u0);
+        if (u1 != 0.f) acc.add(px + 3 * plane, u1);
       }
   };
   // The scan.  Every stripe block passes over all M records of its sample; one event in H / rows is its own.  The warped ROW alone
@@ -909,18 +990,18 @@ __global__ __launch_bounds__(1024) void k_cm_splat_lds(const float4* __restrict_
     float y[CM_CH];
 #pragma unroll
     for (int k = 0; k < CM_CH; ++k) y[k] = yp[min(e0 + k * (int)blockDim.x, M - 1)];  // (clamped: the loads stay unconditional)
-    unsigned acc = 0u;
+    unsigned hits = 0u;
 #pragma unroll
     for (int k = 0; k < CM_CH; ++k)
-      if (e0 + k * (int)blockDim.x < M && mine(y[k])) acc |= 1u << k;
-    while (__builtin_amdgcn_ballot_w64(acc != 0u) != 0ull) {  // (wave-uniform trip count: the loads below sit under no divergent branch)
+      if (e0 + k * (int)blockDim.x < M && mine(y[k])) hits |= 1u << k;
+    while (__builtin_amdgcn_ballot_w64(hits != 0u) != 0ull) {  // (wave-uniform trip count: the loads below sit under no divergent branch)
       int idx[CM_NB];
       bool ok[CM_NB];
 #pragma unroll
       for (int j = 0; j < CM_NB; ++j) {
-        ok[j] = acc != 0u;
-        const int k = ok[j] ? __builtin_ctz(acc) : 0;
-        acc &= acc - 1u;  // (0 stays 0)
+        ok[j] = hits != 0u;
+        const int k = ok[j] ? __builtin_ctz(hits) : 0;
+        hits &= hits - 1u;  // (0 stays 0)
         idx[j] = min(e0 + k * (int)blockDim.x, M - 1);
       }
       float4 w4[CM_NB];
@@ -938,17 +1019,47 @@ __global__ __launch_bounds__(1024) void k_cm_splat_lds(const float4* __restrict_
     }
   }
   __syncthreads();
+  return s;
+}
+
+// The end of a CM stripe block: thread 0 adds the block's two statistics sums at `two` and draws the ticket; true, in every
+// thread, in the block that draws the LAST one -- every block's sums are in memory then.
+// The sums are device-scope ATOMICS (performed at the memory side, never cached) and the last block reads them with device-scope
+// loads, so it is enough that they have COMPLETED before the ticket is drawn: s_waitcnt vmcnt(0) waits for their acknowledgements.
+// No fence does here: a workgroup-scope release lowers to no wait for vector-memory operations (the atomics return nothing, the
+// compiler counts nothing outstanding), and an agent-scope release (__threadfence, or an ACQ_REL ticket) writes the XCD's dirty
+// L2 back -- the image stripes the blocks have just stored, which the finish never reads -- once per block: 51 us of the 205 us
+// launch at 256 x 256 x 4 scales x 8 samples were this.
+__device__ __forceinline__ bool cm_publish_last(float* two, float sq, float nz, unsigned* ticket) {
+  __shared__ int s_last;
+  if (threadIdx.x == 0) {
+    evf_atomic_add(two, sq);
+    evf_atomic_add(two + 1, nz);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = t == gridDim.x * gridDim.y - 1;
+  }
+  __syncthreads();
+  return s_last;
+}
+
+__global__ __launch_bounds__(1024) void k_cm_splat_lds(const float4* __restrict__ warp, const float* __restrict__ tabs,
+                                                       const float* __restrict__ ys, int B, int M, int H, int W, int rows, float P,
+                                                       float* __restrict__ images, CmFin fin) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* img = (float*)smem_raw;
+  const Stripe s = cm_stripe_body(AccFloat{}, img, warp, tabs, ys, B, M, H, W, rows, P);
+  const int sbd = blockIdx.y, d = sbd & 1, plane = s.plane;
   const long HW = (long)H * W;
-  float* o = images + ((long)(sbd >> 1) * 8 + d * 4) * HW + (long)r0 * W;
-  const int n = nr * W;
-  for (int q = threadIdx.x; q < 4 * n; q += blockDim.x) {
+  float* o = images + ((long)(sbd >> 1) * 8 + d * 4) * HW + (long)s.r0 * W;
+  const int n = s.nr * W;
+  for (int q = threadIdx.x; q < 4 * n; q += blockDim.x) {  // (the four planes as one flat copy)
     const int ch = q / n, r = q - ch * n;
     o[(long)ch * HW + r] = img[ch * plane + r];
   }
   if (!fin.stats) return;
   // ---- this stripe's part of the image statistics, straight from LDS (k_cm_reduce re-read the images from memory) ...
   __shared__ float red[16];
-  __shared__ int s_last;
   float sq = 0.f, nz = 0.f;
   for (int p = threadIdx.x; p < n; p += blockDim.x) {
     const float ip = img[p], in = img[plane + p];
@@ -959,29 +1070,13 @@ __global__ __launch_bounds__(1024) void k_cm_splat_lds(const float4* __restrict_
   }
   sq = evf_block_sum(sq, red);
   nz = evf_block_sum(nz, red);
-  if (threadIdx.x == 0) {
-    evf_atomic_add(fin.stats + sbd * 2, sq);
-    evf_atomic_add(fin.stats + sbd * 2 + 1, nz);
-    // The two sums are device-scope ATOMICS (performed at the memory side, never cached) and the last block reads them with
-    // device-scope loads: it is enough that they have COMPLETED before the ticket is drawn -- a workgroup-scope release is that wait
-    // and no cache maintenance.  An agent-scope release here (__threadfence, or an ACQ_REL ticket) writes the XCD's dirty L2 back --
-    // the image stripes the blocks have just stored, which the finish never reads -- once per block: 51 us of the 205 us launch at
-    // 256 x 256 x 4 scales x 8 samples were this.
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    const unsigned t = __hip_atomic_fetch_add(fin.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = t == gridDim.x * gridDim.y - 1;
-  }
-  __syncthreads();
   // ... and the block that arrives last, when every stripe has added its part, finishes the loss (k_cm_finalize)
-  if (s_last) cm_finalize_body(red, fin.stats, fin.part, fin.S, B, fin.Pm, fin.nblk_per_scale, fin.weight, fin.comps,
-                               fin.loss_scaling, fin.loss);
+  if (cm_publish_last(fin.stats + sbd * 2, sq, nz, fin.ticket))
+    cm_finalize_body(red, fin.stats, fin.part, fin.S, B, fin.Pm, fin.nblk_per_scale, fin.weight, fin.comps, fin.loss_scaling, fin.loss);
 }
 
-static int cm_lds_rows(int S, int B, int H, int W) {
-  int rows = 8192 / W;  // 4 planes x rows x W floats <= 128 KiB of LDS
-  if (rows > H) rows = H;
-  while (rows > 8 && (long)S * B * 2 * evf_cdiv(H, rows) < 512) rows >>= 1;  // enough blocks to fill the CUs twice
-  return rows;
+static int cm_lds_rows(int S, int B, int H, int W) {  // 512: enough blocks to fill the CUs twice
+  return stripe_rows(STRIPE_FLOATS, 4, (long)S * B * 2, H, W, 512);
 }
 
 // floats of workspace that make evf_cm_loss_fwd take the LDS-privatised splat (0: image rows too wide for LDS)
@@ -1081,21 +1176,20 @@ __global__ void k_cm_smooth(const float* __restrict__ flow, const float* __restr
 }
 
 // The two loss passes that only read the flow maps -- the pre-warp of the events and the smoothness partials -- in ONE launch
-// (block role by index; 256 threads either way); its first threads also clear `stats` and the ticket of k_cm_splat_lds, which
-// the next launch accumulates into (no fill node).
+// (block role by index; 256 threads either way); its pre-warp blocks also clear the `nclear` words at `clear` -- what the stripe
+// blocks of the next launch add their statistics to: `stats` for k_cm_splat_lds, the per-stripe slots for k_cm_splat_det -- and the
+// ticket (no fill node).
 __global__ __launch_bounds__(256) void k_cm_pre(const float* __restrict__ flow, const float4* __restrict__ ev,
                                                 const float2* __restrict__ pol, const int32_t* __restrict__ ev_pass,
                                                 const float* __restrict__ mask, int S, int Pm, int Pk, int P, int B, int M, int H,
                                                 int W, float Sc, int use_mask, int with_dt, float4* __restrict__ warp,
                                                 float* __restrict__ tabs, float* __restrict__ ys, float* __restrict__ part,
-                                                float* __restrict__ stats, unsigned* __restrict__ ticket, int nbw) {
+                                                float* __restrict__ clear, int nclear, unsigned* __restrict__ ticket, int nbw) {
   __shared__ float red[16];
   const int bid = blockIdx.x;
   if (bid < nbw * S) {
-    if (bid == 0) {
-      for (int i = threadIdx.x; i < S * B * 4; i += blockDim.x) stats[i] = 0.f;
-      if (threadIdx.x == 0) ticket[0] = 0u;
-    }
+    for (long i = (long)bid * blockDim.x + threadIdx.x; i < nclear; i += (long)nbw * S * blockDim.x) clear[i] = 0.f;
+    if (bid == 0 && threadIdx.x == 0) ticket[0] = 0u;
     cm_prewarp_body(bid % nbw, bid / nbw, flow, ev, pol, ev_pass, S, Pm, P, B, M, H, W, Sc, warp, tabs, ys);
     return;
   }
@@ -1157,6 +1251,27 @@ extern "C" int evf_cm_bwd_lds(int mode) {
   return EVF_OK;
 }
 
+// The workspace of the striped CM forward (floats, evf_cm_loss_ws): the pre-warped records [S][B][2][M] x 4, the event times [B][M],
+// the ticket (4 words), the warped rows alone [S][B][2][M], then what the form adds (`rest`: the statistics slots of the exact
+// form).  Also raises KERNEL's dynamic-LDS limit to `lds` bytes if it is below.
+struct CmWs {
+  float4* warp;
+  float* tabs;
+  unsigned* ticket;
+  float *ys, *rest;
+};
+template <auto KERNEL>
+static CmWs cm_fwd_setup(float* ws, int S, int B, int M, size_t lds) {
+  static size_t lds_set = 0;
+  if (lds > lds_set) {
+    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    lds_set = lds;
+  }
+  float* tabs = ws + (size_t)S * B * 2 * M * 4;
+  float* ys = tabs + (size_t)B * M + 4;
+  return {(float4*)ws, tabs, (unsigned*)(tabs + (size_t)B * M), ys, ys + (size_t)S * B * 2 * M};
+}
+
 extern "C" int evf_cm_loss_fwd(const float* flow, const float* ev, const float* pol, const int32_t* ev_pass,
                                const float* mask, int S, int P, int B, int M, int H, int W, float flow_scaling,
                                float regul_weight, int flags, float* images, float* stats, float* smooth_part,
@@ -1175,25 +1290,19 @@ extern "C" int evf_cm_loss_fwd(const float* flow, const float* ev, const float* 
   }();
   int rc = EVF_OK;
   if (ws && evf_cm_loss_ws(S, B, M, H, W) > 0) {
-    float4* warp = (float4*)ws;
-    float* tabs = ws + (size_t)S * B * 2 * M * 4;
-    unsigned* ticket = (unsigned*)(tabs + (size_t)B * M);
-    float* ys = tabs + (size_t)B * M + 4;  // [S][B][2][M]: the warped rows alone
     const int rows = cm_lds_rows(S, B, H, W);
     const size_t lds = (size_t)4 * rows * W * sizeof(float);
-    static size_t lds_set = 0;
-    if (lds > lds_set) {
-      (void)hipFuncSetAttribute((const void*)k_cm_splat_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      lds_set = lds;
-    }
+    const CmWs w = cm_fwd_setup<k_cm_splat_lds>(ws, S, B, M, lds);
+    float4* warp = w.warp;
+    float *tabs = w.tabs, *ys = w.ys;
     if (merge && cm_merge_on) {
       // two launches: [pre-warp | smoothness partials | stats and ticket cleared], [striped splat + image statistics + the
       // last block finishes the loss]
       const int nbw = evf_cdiv((long)B * M, 256);
       hipLaunchKernelGGL(k_cm_pre, dim3(nbw * S + srows * S * Pm * B), dim3(256), 0, st, flow, (const float4*)ev, (const float2*)pol,
                          ev_pass, mask, S, Pm, Pk, P, B, M, H, W, flow_scaling, flags & 1, overwrite ? 0 : 1, warp, tabs, ys, smooth_part,
-                         stats, ticket, nbw);
-      const CmFin fin{stats, ticket, smooth_part, loss, S, Pm, srows * Pm * B, overwrite ? 4 : 5, (flags & 4) ? 1 : 0, regul_weight};
+                         stats, S * B * 4, w.ticket, nbw);
+      const CmFin fin{stats, w.ticket, smooth_part, loss, S, Pm, srows * Pm * B, overwrite ? 4 : 5, (flags & 4) ? 1 : 0, regul_weight};
       hipLaunchKernelGGL(k_cm_splat_lds, dim3(evf_cdiv(H, rows), S * B * 2), dim3(1024), lds, st, (const float4*)warp, tabs, ys, B, M, H, W,
                          rows, (float)P, images, fin);
       return evf_status();
@@ -1224,9 +1333,10 @@ extern "C" int evf_cm_loss_fwd(const float* flow, const float* ev, const float* 
 
 // ---- the deterministic form (evf_cm_loss_fwd_det): exact, order-independent image sums -----------------------------------
 // The float atomics above make a pixel's sum depend on the order in which lanes, waves and blocks deliver its terms.  Here every
-// term is scaled by 2^k (exact), rounded ONCE to a 64-bit integer and added with the LDS integer atomic: integer addition is
-// associative, so the sum is a function of the SET of terms.  k depends on the shape of the call alone (cm_det_scale_log2), never
-// on its data.  The stripes hold 8-byte slots, i.e. half the rows of k_cm_splat_lds; the pre-pass and the scan are that kernel's.
+// term is scaled by 2^k (exact), rounded ONCE to a 64-bit integer and added with the LDS integer atomic (AccFixed): integer addition
+// is associative, so the sum is a function of the SET of terms.  k depends on the shape of the call alone (cm_det_scale_log2), never
+// on its data.  The stripes hold 8-byte slots, i.e. half the rows of k_cm_splat_lds.  The terms are not restated here: the pre-pass
+// is k_cm_pre, and k_cm_splat_det instantiates cm_stripe_body -- zero-fill, taps, products and scan -- as k_cm_splat_lds does.
 // A term is |wt * pol| <= 1 or |wt * tau * pol| <= P for polarity weights in [-1, 1] and event times in [0, 1] within a pass, a
 // pixel receives at most one tap of each of the M events: |sum * 2^k| <= M * P * 2^k < 2^62.
 // THE bit rule of every fixed-point sum of this file: the largest k with terms * ceil(max(bound, 1)) * 2^k < 2^62, for `terms` terms per
@@ -1239,115 +1349,25 @@ static int cm_det_scale_log2(int M, int P) {  // the largest k with M * max(P, 1
   return det_scale_log2((unsigned long long)M, (unsigned long long)(P > 1 ? P : 1));
 }
 #define CM_DET_MIN_LOG2 32  // fewer fraction bits than this: refused (M * P >= 2^30)
-static int cm_det_rows(int S, int B, int H, int W) {
-  int rows = 4096 / W;  // 4 planes x rows x W 64-bit slots <= 128 KiB of LDS
-  if (rows > H) rows = H;
-  while (rows > 8 && (long)S * B * 2 * evf_cdiv(H, rows) < 512) rows >>= 1;  // (the rule of cm_lds_rows)
-  return rows;
-}
-
-// k_cm_pre with the per-stripe statistics slots of k_cm_splat_det to clear instead of `stats` (the pre-warp blocks share the work)
-__global__ __launch_bounds__(256) void k_cm_pre_det(const float* __restrict__ flow, const float4* __restrict__ ev,
-                                                    const float2* __restrict__ pol, const int32_t* __restrict__ ev_pass,
-                                                    const float* __restrict__ mask, int S, int Pm, int Pk, int P, int B, int M, int H,
-                                                    int W, float Sc, int use_mask, int with_dt, float4* __restrict__ warp,
-                                                    float* __restrict__ tabs, float* __restrict__ ys, float* __restrict__ part,
-                                                    float* __restrict__ slots, int nslots, unsigned* __restrict__ ticket, int nbw) {
-  __shared__ float red[16];
-  const int bid = blockIdx.x;
-  if (bid < nbw * S) {
-    for (long i = (long)bid * blockDim.x + threadIdx.x; i < nslots; i += (long)nbw * S * blockDim.x) slots[i] = 0.f;
-    if (bid == 0 && threadIdx.x == 0) ticket[0] = 0u;
-    cm_prewarp_body(bid % nbw, bid / nbw, flow, ev, pol, ev_pass, S, Pm, P, B, M, H, W, Sc, warp, tabs, ys);
-    return;
-  }
-  const int sb = bid - nbw * S, gx = (H + SM_ROWS - 1) / SM_ROWS;
-  cm_smooth_body(sb % gx, sb / gx, gx, red, flow, mask, Pm, Pk, B, H, W, use_mask, with_dt, part);
-}
+static int cm_det_rows(int S, int B, int H, int W) { return stripe_rows(SPLAT_DET_SLOTS, 4, (long)S * B * 2, H, W, 512); }
 
 __global__ __launch_bounds__(1024) void k_cm_splat_det(const float4* __restrict__ warp, const float* __restrict__ tabs,
                                                        const float* __restrict__ ys, int B, int M, int H, int W, int rows, float P,
                                                        int k2, float* __restrict__ images, float* __restrict__ slots, CmFin fin) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  unsigned long long* img = (unsigned long long*)smem_raw;  // [4][rows*W] two's complement: I_pos, I_neg, TS_pos, TS_neg of this direction
-  const int sbd = blockIdx.y, d = sbd & 1, b = (sbd >> 1) % B;
-  const int r0 = blockIdx.x * rows, nr = min(rows, H - r0), plane = rows * W;
-  for (int q = threadIdx.x; q < 4 * plane; q += blockDim.x) img[q] = 0ull;
-  __syncthreads();
-  const float4* __restrict__ wp = warp + (long)sbd * M;
-  const float* __restrict__ tb = tabs + (long)b * M;
-  const float lo = (float)r0, hi = (float)(r0 + nr), fW = (float)W;
-  auto fix = [&](float v) { return (unsigned long long)__float2ll_rn(ldexpf(v, k2)); };  // (ldexpf: an exact scaling)
-  auto one = [&](const float4 w4, const float t) {  // (the weights and products of k_cm_splat_lds, term for term)
-    const float tau = d ? P - t : t;
-    const float cy[2] = {floorf(w4.x), floorf(w4.x + 1.0f)};
-    const float cx[2] = {floorf(w4.y), floorf(w4.y + 1.0f)};
-    float ay[2], ax[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      ay[k] = fmaxf(0.f, 1.0f - fabsf(w4.x - cy[k]));
-      ax[k] = fmaxf(0.f, 1.0f - fabsf(w4.y - cx[k]));
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        if (!(cy[j] >= lo && cy[j] < hi && cx[i] >= 0.f && cx[i] < fW)) continue;  // other stripes / outside (NaN too)
-        const float wt = ay[j] * ax[i];
-        if (wt == 0.f) continue;
-        unsigned long long* px = img + ((int)cy[j] - r0) * W + (int)cx[i];
-        const float wtau = wt * tau;
-        const float v0 = wt * w4.z, v1 = wt * w4.w, u0 = wtau * w4.z, u1 = wtau * w4.w;
-        if (v0 != 0.f) atomicAdd(px, fix(v0));
-        if (v1 != 0.f) atomicAdd(px + plane, fix(v1));
-        if (u0 != 0.f) atomicAdd(px + 2 * plane, fix(u0));
-        if (u1 != 0.f) atomicAdd(px + 3 * plane, fix(u1));
-      }
-  };
-  // the scan of k_cm_splat_lds: the warped row alone decides, the accepted records are fetched CM_NB at a time
-  const float* __restrict__ yp = ys + (long)sbd * M;
-  auto mine = [&](float y) {
-    const float c0 = floorf(y), c1 = floorf(y + 1.0f);
-    return (c0 >= lo && c0 < hi) || (c1 >= lo && c1 < hi);
-  };
-  for (int e0 = threadIdx.x; e0 < M; e0 += CM_CH * (int)blockDim.x) {
-    float y[CM_CH];
-#pragma unroll
-    for (int k = 0; k < CM_CH; ++k) y[k] = yp[min(e0 + k * (int)blockDim.x, M - 1)];
-    unsigned acc = 0u;
-#pragma unroll
-    for (int k = 0; k < CM_CH; ++k)
-      if (e0 + k * (int)blockDim.x < M && mine(y[k])) acc |= 1u << k;
-    while (__builtin_amdgcn_ballot_w64(acc != 0u) != 0ull) {
-      int idx[CM_NB];
-      bool ok[CM_NB];
-#pragma unroll
-      for (int j = 0; j < CM_NB; ++j) {
-        ok[j] = acc != 0u;
-        const int k = ok[j] ? __builtin_ctz(acc) : 0;
-        acc &= acc - 1u;
-        idx[j] = min(e0 + k * (int)blockDim.x, M - 1);
-      }
-      float4 w4[CM_NB];
-      float tt[CM_NB];
-#pragma unroll
-      for (int j = 0; j < CM_NB; ++j) w4[j] = wp[idx[j]], tt[j] = tb[idx[j]];
-#pragma unroll
-      for (int j = 0; j < CM_NB; ++j)
-        if (ok[j]) one(w4[j], tt[j]);
-    }
-  }
-  __syncthreads();
+  AccFixed::slot* img = (AccFixed::slot*)smem_raw;
+  const AccFixed acc{k2};
+  const Stripe s = cm_stripe_body(acc, img, warp, tabs, ys, B, M, H, W, rows, P);
+  const int sbd = blockIdx.y, d = sbd & 1, plane = s.plane;
   // write-out: every sum converted ONCE, (float)sum * 2^-k, into the layout of k_cm_splat_lds; the statistics from the same floats
   const long HW = (long)H * W;
-  float* o = images + ((long)(sbd >> 1) * 8 + d * 4) * HW + (long)r0 * W;
-  const int n = nr * W;
+  float* o = images + ((long)(sbd >> 1) * 8 + d * 4) * HW + (long)s.r0 * W;
+  const int n = s.nr * W;
   __shared__ float red[16];
-  __shared__ int s_last;
   float sq = 0.f, nz = 0.f;
   for (int p = threadIdx.x; p < n; p += blockDim.x) {
-    const float ip = ldexpf(__ll2float_rn((long long)img[p]), -k2), in = ldexpf(__ll2float_rn((long long)img[plane + p]), -k2);
-    const float tp = ldexpf(__ll2float_rn((long long)img[2 * plane + p]), -k2), tn = ldexpf(__ll2float_rn((long long)img[3 * plane + p]), -k2);
+    const float ip = acc.get(img + p), in = acc.get(img + plane + p);
+    const float tp = acc.get(img + 2 * plane + p), tn = acc.get(img + 3 * plane + p);
     o[p] = ip, o[HW + p] = in, o[2 * HW + p] = tp, o[3 * HW + p] = tn;
     const float ap = tp / (ip + 1e-9f) / P;  // loss/flow.py:212-215
     const float an = tn / (in + 1e-9f) / P;
@@ -1356,19 +1376,10 @@ __global__ __launch_bounds__(1024) void k_cm_splat_det(const float4* __restrict_
   }
   sq = evf_block_sum(sq, red);  // (fixed order: the butterfly of the wave, then the waves by index)
   nz = evf_block_sum(nz, red);
-  if (threadIdx.x == 0) {
-    // One slot per (scale, sample, direction, stripe), zeroed by k_cm_pre_det: this block is its only writer, 0 + x is exact and has
-    // no order.  Device-scope atomics all the same, for the memory-model argument of k_cm_splat_lds: performed at the memory side,
-    // complete at the workgroup-scope release, read by the last block with device-scope loads -- no agent-scope fence.
-    float* sl = slots + ((long)sbd * gridDim.x + blockIdx.x) * 2;
-    evf_atomic_add(sl, sq);
-    evf_atomic_add(sl + 1, nz);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    const unsigned t = __hip_atomic_fetch_add(fin.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = t == gridDim.x * gridDim.y - 1;
-  }
-  __syncthreads();
-  if (!s_last) return;
+  // One slot per (scale, sample, direction, stripe), zeroed by k_cm_pre: this block is its only writer, 0 + x is exact and has no
+  // order.  Device-scope atomics all the same, for the memory-model argument of cm_publish_last: performed at the memory side,
+  // complete before the ticket is drawn, read by the last block with device-scope loads -- no agent-scope fence.
+  if (!cm_publish_last(slots + ((long)sbd * gridDim.x + blockIdx.x) * 2, sq, nz, fin.ticket)) return;
   // the last block: the stripes' parts in STRIPE INDEX order into `stats`, then the loss (cm_finalize_body: smoothness partials and
   // statistics by thread-strided loops and evf_block_sum, the scales in sequence on thread 0 -- a fixed order as well)
   const int nst = gridDim.x;
@@ -1405,36 +1416,28 @@ extern "C" int evf_cm_loss_fwd_det(const float* flow, const float* ev, const flo
   const int overwrite = (flags & 2) ? 1 : 0;
   const int Pm = overwrite ? 1 : P, Pk = Pm;
   const int srows = evf_cdiv(H, SM_ROWS);
-  float4* warp = (float4*)ws;
-  float* tabs = ws + (size_t)S * B * 2 * M * 4;
-  unsigned* ticket = (unsigned*)(tabs + (size_t)B * M);
-  float* ys = tabs + (size_t)B * M + 4;
-  float* slots = ys + (size_t)S * B * 2 * M;
   const int rows = cm_det_rows(S, B, H, W), nst = evf_cdiv(H, rows);
-  const size_t lds = (size_t)4 * rows * W * sizeof(unsigned long long);
-  static size_t lds_set = 0;
-  if (lds > lds_set) {
-    (void)hipFuncSetAttribute((const void*)k_cm_splat_det, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    lds_set = lds;
-  }
+  const size_t lds = (size_t)4 * rows * W * sizeof(AccFixed::slot);
+  const CmWs w = cm_fwd_setup<k_cm_splat_det>(ws, S, B, M, lds);
+  float* slots = w.rest;  // [S][B][2][nst][2]
   // always the two merged launches, whatever the event count (evf_cm_merge and the caller's size threshold do not apply)
   const int nbw = evf_cdiv((long)B * M, 256);
-  hipLaunchKernelGGL(k_cm_pre_det, dim3(nbw * S + srows * S * Pm * B), dim3(256), 0, st, flow, (const float4*)ev, (const float2*)pol,
-                     ev_pass, mask, S, Pm, Pk, P, B, M, H, W, flow_scaling, flags & 1, overwrite ? 0 : 1, warp, tabs, ys, smooth_part,
-                     slots, S * B * 2 * nst * 2, ticket, nbw);
-  const CmFin fin{stats, ticket, smooth_part, loss, S, Pm, srows * Pm * B, overwrite ? 4 : 5, (flags & 4) ? 1 : 0, regul_weight};
-  hipLaunchKernelGGL(k_cm_splat_det, dim3(nst, S * B * 2), dim3(1024), lds, st, (const float4*)warp, tabs, ys, B, M, H, W, rows,
+  hipLaunchKernelGGL(k_cm_pre, dim3(nbw * S + srows * S * Pm * B), dim3(256), 0, st, flow, (const float4*)ev, (const float2*)pol,
+                     ev_pass, mask, S, Pm, Pk, P, B, M, H, W, flow_scaling, flags & 1, overwrite ? 0 : 1, w.warp, w.tabs, w.ys,
+                     smooth_part, slots, S * B * 2 * nst * 2, w.ticket, nbw);
+  const CmFin fin{stats, w.ticket, smooth_part, loss, S, Pm, srows * Pm * B, overwrite ? 4 : 5, (flags & 4) ? 1 : 0, regul_weight};
+  hipLaunchKernelGGL(k_cm_splat_det, dim3(nst, S * B * 2), dim3(1024), lds, st, (const float4*)w.warp, w.tabs, w.ys, B, M, H, W, rows,
                      (float)P, cm_det_scale_log2(M, P), images, slots, fin);
   return evf_status();
 }
 
 // ---- the deterministic forms of the voxel binning and of the IWE splat (evf_encode_*_det, evf_iwe_splat_det) ---------------------
 // The technique of k_cm_splat_det for the two other float-atomic sums whose terms have a bound known from the call's shape: a block
-// owns a stripe of rows of ONE sample, all planes, as signed 64-bit LDS slots; it scans that sample's events (L2 resident), computes
-// every term in fp32 exactly as the default kernel does, scales it by 2^k (ldexpf: exact), rounds ONCE (__float2ll_rn) and adds with
-// the 64-bit LDS integer atomic; the stripe is converted once and stored coalesced.  No zero-fill launch, no global atomic, no
-// ticket, no workspace.  k = det_scale_log2(terms per slot, bound of a term): shape and declared bounds, never data.
-#define SPLAT_DET_SLOTS 16384  // 64-bit slots of a stripe: 128 KiB of LDS
+// owns a stripe of rows of ONE sample, all planes, as signed 64-bit LDS slots (AccFixed); it scans that sample's events (L2
+// resident), computes every term in fp32 as the default kernel does -- k_iwe_splat_det by instantiating the body of k_iwe_splat_lds,
+// iwe_stripe_body, not by restating it --, scales it by 2^k, rounds ONCE and adds with the 64-bit LDS integer atomic; the stripe is
+// converted once and stored coalesced (stripe_out).  No zero-fill launch, no global atomic, no ticket, no workspace.
+// k = det_scale_log2(terms per slot, bound of a term): shape and declared bounds, never data.
 
 extern "C" int evf_splat_det_bits(int64_t terms_per_slot, float bound) {
   if (terms_per_slot <= 0 || !(bound >= 0.f) || !(bound < INFINITY)) return EVF_EINVAL;
@@ -1444,22 +1447,7 @@ extern "C" int evf_splat_det_bits(int64_t terms_per_slot, float bound) {
   return k >= CM_DET_MIN_LOG2 ? k : EVF_ENOTSUP;
 }
 
-// rows of a stripe of `planes` planes of width W: what the LDS holds, capped at H, halved while above 8 and the grid is short of
-// blocks (the rule of cm_det_rows); 0: a single row does not fit
-static int splat_det_rows(int samples, int planes, int H, int W) {
-  if ((long)planes * W > SPLAT_DET_SLOTS) return 0;
-  int rows = SPLAT_DET_SLOTS / (planes * W);
-  if (rows > H) rows = H;
-  while (rows > 8 && (long)samples * evf_cdiv(H, rows) < 512) rows >>= 1;
-  return rows;
-}
-
-// the stripe's sums -> floats, every sum converted ONCE: planes [nplanes][H*W] of one sample at `o`, rows r0 .. r0 + nr
-__device__ __forceinline__ void det_stripe_out(const unsigned long long* __restrict__ img, int nplanes, int plane, int n, int k2,
-                                               float* __restrict__ o, long HW) {
-  for (int c = 0; c < nplanes; ++c)
-    for (int q = threadIdx.x; q < n; q += blockDim.x) o[c * HW + q] = ldexpf(__ll2float_rn((long long)img[c * plane + q]), -k2);
-}
+static int splat_det_rows(int samples, int planes, int H, int W) { return stripe_rows(SPLAT_DET_SLOTS, planes, samples, H, W, 512); }
 
 // Voxel grid of k_encode_events / k_encode_window (dataloader/encodings.py:48-67).  Sample blockIdx.y = b * P + pp of ev [B][P][N]
 // goes to plane set pp * B + b of voxel (P = 1: batch-major [B][nb][H][W]; else pass-major [P][B][nb][H][W]).  An event belongs to
@@ -1490,7 +1478,7 @@ __global__ __launch_bounds__(1024) void k_voxel_det(const float4* __restrict__ e
   }
   __syncthreads();
   const long HW = (long)H * W;
-  det_stripe_out(img, nb, plane, nr * W, k2, voxel + ((long)pp * B + b) * nb * HW + (long)r0 * W, HW);
+  stripe_out(AccFixed{k2}, img, nb, plane, nr * W, voxel + ((long)pp * B + b) * nb * HW + (long)r0 * W, HW);
 }
 
 // the refusals and the launch of k_voxel_det, shared by the two entry points; `samples` = B * P
@@ -1555,12 +1543,10 @@ extern "C" int evf_encode_window_det(const float* ev, int B, int P, int N, int H
   return evf_status();
 }
 
-// evf_iwe_splat for every mode / nch / map_of_event / ts_shift / weight combination: per event the flow gather, `flow * 0`, the
-// warp and the taps and products of evf_splat<ROUND>, term for term; only the accumulation differs.  A pixel receives at most one
-// tap of an event, so a slot holds at most M terms: |w * a| <= 1 for weights in [-1, 1], |w * tau * a| <= tau_bound.  The warped
-// row(s) decide whether an event is this stripe's.  Taps with non-finite coordinates are skipped (the default path lets NaN into
-// the image: non-finite flow is outside this mode's contract), and so is an event whose own pixel lies outside the flow map (the
-// default path reads out of bounds there).
+// evf_iwe_splat for every mode / nch / map_of_event / ts_shift / weight combination: iwe_stripe_body, the body of k_iwe_splat_lds,
+// with exact sums -- the same terms because it is the same code; what the exact form does differently is listed at that body.  A
+// pixel receives at most one tap of an event, so a slot holds at most M terms: |w * a| <= 1 for weights in [-1, 1],
+// |w * tau * a| <= tau_bound.
 template <bool ROUND>
 __global__ __launch_bounds__(1024) void k_iwe_splat_det(const float* __restrict__ flow, const float4* __restrict__ ev,
                                                         const int32_t* __restrict__ map_of_event,
@@ -1568,95 +1554,8 @@ __global__ __launch_bounds__(1024) void k_iwe_splat_det(const float* __restrict_
                                                         const float* __restrict__ w1, int wstride, int B, int M, int H, int W,
                                                         float S, float tref, float tref_ts, int mode, int nch, int rows, int k2,
                                                         float* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  unsigned long long* img = (unsigned long long*)smem_raw;  // [nch][rows*W] two's complement
-  const int b = blockIdx.y, r0 = blockIdx.x * rows;
-  const int nr = min(rows, H - r0), plane = rows * W;
-  for (int q = threadIdx.x; q < nch * plane; q += blockDim.x) img[q] = 0ull;
-  __syncthreads();
-  const long HW = (long)H * W;
-  const float lo = (float)r0, hi = (float)(r0 + nr), fW = (float)W;
-  auto put = [&](unsigned long long* px, float v) {
-    if (v != 0.f) atomicAdd(px, (unsigned long long)__float2ll_rn(ldexpf(v, k2)));
-  };
-#define IWD_U 4  // (events in batches, as in k_iwe_splat_lds: the event loads, then the gathers that depend on them)
-  for (int e0 = threadIdx.x; e0 < M; e0 += IWD_U * blockDim.x) {
-    float4 qs[IWD_U];
-    float ts[IWD_U], fys[IWD_U], fxs[IWD_U];
-    bool ok[IWD_U];
-#pragma unroll
-    for (int u = 0; u < IWD_U; ++u) {
-      const int e = min(e0 + u * (int)blockDim.x, M - 1);  // clamped: loads stay unconditional
-      qs[u] = ev[(long)b * M + e];
-      ts[u] = ts_shift ? (float)ts_shift[e] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < IWD_U; ++u) {
-      const int e = min(e0 + u * (int)blockDim.x, M - 1);
-      const float lin = qs[u].y * fW + qs[u].z;  // the index of evf_event_flow, checked before it is used
-      ok[u] = e0 + u * (int)blockDim.x < M && lin > -1.0f && lin < (float)HW;
-      fys[u] = fxs[u] = 0.f;
-      if (ok[u]) evf_event_flow(flow, map_of_event ? map_of_event[e] : 0, B, b, HW, qs[u].y, qs[u].z, W, fys[u], fxs[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < IWD_U; ++u) {
-      if (!ok[u]) continue;
-      const float4 q = qs[u];
-      const float t = q.x + ts[u];
-      float fy = fys[u], fx = fxs[u];
-      if (mode & 2) {  // `flow * 0`
-        fy *= 0.f;
-        fx *= 0.f;
-      }
-      const float tau = (mode & 8) ? (tref_ts - t) : t;
-      const Warp w = evf_warp(t, q.y, q.z, fy, fx, tref, S);
-      const long i = (long)b * M + e0 + u * (int)blockDim.x;
-      if (ROUND) {
-        const float iy = rintf(w.wy), ix = rintf(w.wx);
-        if (!(iy >= lo && iy < hi && ix >= 0.f && ix < fW)) continue;  // other stripes / outside (NaN too)
-        const float a0 = w0 ? w0[i * wstride] : 1.0f;
-        const float a1 = w1 ? w1[i * wstride] : 0.0f;
-        unsigned long long* px = img + ((int)iy - r0) * W + (int)ix;
-        put(px, a0);
-        if (nch >= 2) put(px + plane, a1);
-        if (nch == 4) {
-          put(px + 2 * plane, tau * a0);
-          put(px + 3 * plane, tau * a1);
-        }
-      } else {
-        const float cy[2] = {floorf(w.wy), floorf(w.wy + 1.0f)};
-        const float cx[2] = {floorf(w.wx), floorf(w.wx + 1.0f)};
-        if (!((cy[0] >= lo && cy[0] < hi) || (cy[1] >= lo && cy[1] < hi))) continue;
-        const float a0 = w0 ? w0[i * wstride] : 1.0f;
-        const float a1 = w1 ? w1[i * wstride] : 0.0f;
-        float ay[2], ax[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          ay[k] = fmaxf(0.f, 1.0f - fabsf(w.wy - cy[k]));
-          ax[k] = fmaxf(0.f, 1.0f - fabsf(w.wx - cx[k]));
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int k = 0; k < 2; ++k) {
-            if (!(cy[j] >= lo && cy[j] < hi && cx[k] >= 0.f && cx[k] < fW)) continue;
-            const float wt = ay[j] * ax[k];
-            if (wt == 0.f) continue;
-            unsigned long long* px = img + ((int)cy[j] - r0) * W + (int)cx[k];
-            put(px, wt * a0);
-            if (nch >= 2) put(px + plane, wt * a1);
-            if (nch == 4) {
-              const float wtau = wt * tau;
-              put(px + 2 * plane, wtau * a0);
-              put(px + 3 * plane, wtau * a1);
-            }
-          }
-      }
-    }
-  }
-#undef IWD_U
-  __syncthreads();
-  det_stripe_out(img, nch, plane, nr * W, k2, out + (long)b * nch * HW + (long)r0 * W, HW);
+  iwe_stripe_body<ROUND>(AccFixed{k2}, flow, ev, map_of_event, ts_shift, w0, w1, wstride, B, M, H, W, S, tref, tref_ts, mode, nch,
+                         rows, out);
 }
 
 extern "C" int evf_iwe_splat_det(const float* flow, const float* ev, const int32_t* map_of_event, const int32_t* ts_shift,

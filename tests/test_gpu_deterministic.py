@@ -234,6 +234,45 @@ def test_c_deterministic_path_matches_the_default_path(name):
             assert np.abs(a - b).max() <= 1e-5 * max(np.abs(a).max(), 1e-12), (name, np.abs(a - b).max(), np.abs(a).max())
 
 
+def test_c_default_stripe_images_equal_the_exact_sum_images(monkeypatch):
+    """k_cm_splat_lds against k_cm_splat_det bit for bit where the sums are fractional.  Dyadic inputs (event times in 1/8, flows
+    in 1/64 with flow_scaling 128, polarities +-1 on a few shared columns: warped coordinates in 1/4, terms in 2^-7, 1800 of them
+    per sample), so every partial sum of an image is exact in fp32 and the float atomics have no order to depend on: the images
+    must be EQUAL.  B = 2, 37 x 53, two passes of 900 events, two scales: stripes of 4 rows and a last one of 1 in both forms.
+    The default's statistics are float atomics over non-dyadic squares: the losses agree to rtol 1e-6, not bitwise."""
+    B, H, W, P, n, S = 2, 37, 53, 2, 900, 2
+    monkeypatch.setattr(hloss, "CM_LDS_MIN_EVENTS", 0)  # (7200 event-scale pairs: the default call takes the stripe kernel all the same)
+    rng = np.random.default_rng(23)
+    evs, pols, flows = [], [], []
+    for _ in range(P):
+        ev = np.empty((B, n, 4), np.float32)
+        ev[:, :, 0] = rng.integers(0, 9, size=(B, n)) / 8.0
+        ev[:, :, 1] = rng.integers(0, H, size=(B, n))
+        ev[:, :, 2] = rng.integers(0, 12, size=(B, n)) + 20
+        ev[:, :, 3] = rng.integers(0, 2, size=(B, n)) * 2 - 1
+        evs.append(ev)
+        pols.append(np.stack([ev[:, :, 3] > 0, ev[:, :, 3] < 0], 2).astype(np.float32))
+        flows.append([(rng.integers(-12, 13, size=(B, 2, H, W)) / 64.0).astype(np.float32) for _ in range(S)])
+    got = {}
+    before = _lib.deterministic()
+    try:
+        for on in (False, True):
+            _lib.set_deterministic(on)
+            lossf = hloss.EventWarping(cfg(H, W), DEV, flow_scaling=128)
+            for k in range(P):
+                lossf.event_flow_association([G(f).requires_grad_(True) for f in flows[k]], G(evs[k]), G(pols[k]),
+                                             torch.ones(B, 1, H, W, device=DEV))
+            val = lossf()
+            got[on] = (N(val.grad_fn.saved_tensors[1]).copy(), N(val).copy())
+    finally:
+        _lib.set_deterministic(before)
+    (im_p, loss_p), (im_d, loss_d) = got[False], got[True]
+    assert im_p.shape == (S, B, 8, H, W) and np.isfinite(im_p).all()
+    assert (im_d[:, :, :, H - 1] != 0).any()  # (the short last stripe holds terms)
+    assert np.array_equal(im_p, im_d)
+    np.testing.assert_allclose(loss_p, loss_d, rtol=1e-6)
+
+
 # ------------------------------------------------------------------ accuracy against float64
 def _float64(win):
     B, H, W, P, S = (win[k] for k in "BHWPS")

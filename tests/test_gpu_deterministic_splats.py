@@ -427,6 +427,34 @@ def test_5_known_answers_exact_in_fp32(det_on):
         assert np.array_equal(got, ref64.astype(np.float32)), rnd
 
 
+def test_5_default_stripe_kernel_equals_the_exact_sum_kernel():
+    """k_iwe_splat_lds against k_iwe_splat_det bit for bit where the sums are fractional: the dyadic inputs of the test above at
+    B x n = 32 x 12517 = 400544 events (>= 400000: the default call takes the stripe kernel; n is no multiple of 4 x 1024: the
+    clamped tail batch runs; 37 rows: stripes of 5 and a last one of 2).  12517 terms of at most 21 significant bits: every partial
+    sum is exact in fp32 -- the float64 evaluation is its own fp32 rounding --, so the float atomics have no order to depend on and
+    default == deterministic == float64, signed weights, four planes, rounded and bilinear."""
+    B, n, H, W = 32, 12517, 37, 53
+    rng = np.random.default_rng(22)
+    ev = np.empty((B, n, 4), np.float32)
+    ev[:, :, 0] = rng.integers(0, 9, size=(B, n)) / 8.0
+    ev[:, :, 1] = rng.integers(0, H, size=(B, n))
+    ev[:, :, 2] = rng.integers(0, 12, size=(B, n)) + 20
+    pm = rng.integers(0, 2, size=(B, n)) * 2 - 1
+    sgn, neg = pm.astype(np.float32), (pm < 0).astype(np.float32)
+    flow = (rng.integers(-12, 13, size=(B, 2, H, W)) / 64.0).astype(np.float32)
+    gf, ge, g0, g1 = G(flow), G(ev), G(sgn), G(neg)
+    for rnd in (False, True):
+        ref64 = iwe_f64(flow, ev, H, W, 128.0, 1.0, sgn, neg, 4, rnd)
+        assert np.array_equal(ref64.astype(np.float32).astype(np.float64), ref64)
+        assert (ref64[:, 0] < 0).any() and (ref64[:, 0] > 0).any() and (ref64[:, :, 35:] != 0).any()  # (the short last stripe too)
+        out = {}
+        for on in (False, True):
+            with mode(on):
+                out[on] = N(hiwe.iwe_splat(gf, ge, (H, W), 128, 1.0, round_idx=rnd, w0=g0, w1=g1, nch=4, with_ts=True))
+        assert np.array_equal(out[False], out[True]), rnd
+        assert np.array_equal(out[True], ref64.astype(np.float32)), rnd
+
+
 # ------------------------------------------------------------------ 6: accuracy against float64
 def test_6_accuracy_against_float64_is_that_of_the_default_path():
     """Voxel grids and bilinear images (counts and timestamps) of two windows evaluated in float64; the default and the deterministic
