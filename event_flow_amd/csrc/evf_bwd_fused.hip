@@ -762,6 +762,14 @@ __device__ __forceinline__ void fb_body_ws(
     const float4* ppp = (PLIF && pl.pt_prev) ? pl.pt_prev : v_out;
     const bool has_gk = PLIF && pl.gpt_carry != nullptr, has_pp = PLIF && pl.pt_prev != nullptr;
     // stage 1: the global loads of half h of unit k (straight-line, unconditional, clamped: see fb_body)
+    // TOP (`head_planes`): the head's operands ONCE per pixel.  The 8 lanes of a pixel (cg = 0..7, one clamped pixel pc for all of
+    // them) used to request flow x / y, dL/dflow x / y and the spike word each: five vector-memory instructions of which team E's
+    // sibling without the head issues none.  Now a lane requests the component cg & 1 only (FbStage::f0 / q0; the lanes of one
+    // parity share a dword, so no lane needs a dummy address or a branch) -- three instructions -- and commit() forms the
+    // lane's own tanh' product and reads gp0 / gp1 from the even / odd lane of its pair by two quad-permute DPP moves (vector
+    // unit only: the LDS pipe is team M's; no select, no lane mask held in scalar registers).  Same expression on the same
+    // values: gp0 / gp1 keep their bits.  (With lane ^ 1's product and two selects by lane parity instead, the ALIF top spilled
+    // two more vector registers; this form adds a spill to no instantiation.)
     auto issue = [&](const int k, const int h, FbStage& s, FbStagePlif& sp) {
       int b, y, x0, cw;
       int ku = k, ks = 0;  // unit of the block, pass (WIN)
@@ -781,8 +789,8 @@ __device__ __forceinline__ void fb_body_ws(
         if (TOP) {
           const long hw = (long)H * W, q = (long)y * W + x0 + pc;
           const float *wf = wp->flow[ks], *wg = wp->g_flow[ks];
-          s.f0 = wf[(long)b * 2 * hw + q], s.f1 = wf[((long)b * 2 + 1) * hw + q];
-          s.q0 = wg[(long)b * 2 * hw + q], s.q1 = wg[((long)b * 2 + 1) * hw + q];
+          const long fq = (long)b * 2 * hw + q + ((cg & 1) ? hw : 0);  // (ONE component per lane, see `head_planes`)
+          s.f0 = wf[fq], s.q0 = wg[fq];
           s.zo = wp->z_out[ks][pix0 + pc];
         } else
           s.gz = (wgz ? wgz : wvo)[ge];
@@ -805,8 +813,8 @@ __device__ __forceinline__ void fb_body_ws(
       s.vo = v_out[ge];
       if (TOP) {
         const long hw = (long)H * W, q = (long)y * W + x0 + pc;
-        s.f0 = top.flow[(long)b * 2 * hw + q], s.f1 = top.flow[((long)b * 2 + 1) * hw + q];
-        s.q0 = top.g_flow[(long)b * 2 * hw + q], s.q1 = top.g_flow[((long)b * 2 + 1) * hw + q];
+        const long fq = (long)b * 2 * hw + q + ((cg & 1) ? hw : 0);
+        s.f0 = top.flow[fq], s.q0 = top.g_flow[fq];
         s.zo = top.z_out[pix0 + pc];
       } else {
         s.gz = pgz[ge];
@@ -852,8 +860,10 @@ __device__ __forceinline__ void fb_body_ws(
       const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
       float gp0 = 0.f, gp1 = 0.f;
       if (TOP) {
-        gp0 = s.q0 * (1.0f - s.f0 * s.f0);  // tanh' (evf_pred_bwd)
-        gp1 = s.q1 * (1.0f - s.f1 * s.f1);
+        const int gpo = __float_as_int(s.q0 * (1.0f - s.f0 * s.f0));  // tanh' (evf_pred_bwd) of the lane's component, cg & 1 (`head_planes`)
+        gp0 = __int_as_float(__builtin_amdgcn_mov_dpp(gpo, 0xA0, 0xF, 0xF, true));  // quad_perm [0,0,2,2]: the even lane's = x
+        gp1 = __int_as_float(__builtin_amdgcn_mov_dpp(gpo, 0xF5, 0xF, 0xF, true));  // quad_perm [1,1,3,3]: the odd lane's = y
+        asm volatile("" : "+v"(gp0), "+v"(gp1));  // (pinned here, every lane active: never sunk into a branch some lanes of the quad skip)
       }
       const float4 gz4 = TOP ? make_float4(gp0 * pwa[0] + gp1 * pwb[0], gp0 * pwa[1] + gp1 * pwb[1], gp0 * pwa[2] + gp1 * pwb[2],
                                            gp0 * pwa[3] + gp1 * pwb[3])

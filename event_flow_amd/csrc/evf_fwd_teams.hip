@@ -721,22 +721,48 @@ __device__ __forceinline__ void ft_body(const JOBS& jobs, const FtPlan& plan, co
           asm volatile("" ::"v"(word));
 #endif
           if (has_pred) {  // (cell-uniform) the prediction head on this pixel's spike word, summed like evf_pred_fwd
-            float s0 = 0.f, s1 = 0.f;
+            if constexpr (!PLIF && (FULL || WIN)) {
+              // ONE flow component per lane: the publishing lane 8g + 4 + kq hands pixel vi's word to lane 8g + kq (one more DPP
+              // move) and keeps the x component, the lower lane takes y -- each still the sequential sum over channels 0..31 (z
+              // is 0 or 1, so the product is exact and the fused multiply-add rounds like evf_pred_fwd's multiply, then add).
+              // Per lane 8 LDS reads, 32 multiply-adds and one tanhf, where half of the lanes had 16, 64 and two and the other
+              // half ran the same loop for nothing; the LDS pipe is this kernel's limit.
+              uint32_t wup = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)word, 0x104, 0xF, 0xF, true);  // row_shl:4: lane + 4's word
+              // (pinned here, with every lane active: as an operand of the select below the compiler sank the move into a branch
+              // taken by the lower lanes only, where it reads the switched-off publishing lanes as 0)
+              asm volatile("" : "+v"(wup));
+              const uint32_t hword = pub ? word : wup;
+              const float* s_pwl = s_pw + (pub ? 0 : C32);
+              float s = 0.f;
 #pragma unroll 1
-            for (int cc = 0; cc < C32; cc += 4) {
-              const float4 pa = *(const float4*)(s_pw + cc), pb4 = *(const float4*)(s_pw + C32 + cc);
-              const float pa4[4] = {pa.x, pa.y, pa.z, pa.w}, pb44[4] = {pb4.x, pb4.y, pb4.z, pb4.w};
+              for (int cc = 0; cc < C32; cc += 8) {
+                const float4 pa = *(const float4*)(s_pwl + cc), pb4 = *(const float4*)(s_pwl + cc + 4);
+                const float pw8[8] = {pa.x, pa.y, pa.z, pa.w, pb4.x, pb4.y, pb4.z, pb4.w};
 #pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const float z = (float)((word >> (cc + q)) & 1u);
-                s0 += z * pa4[q];
-                s1 += z * pb44[q];
+                for (int q = 0; q < 8; ++q) s = __builtin_fmaf((float)((hword >> (cc + q)) & 1u), pw8[q], s);
               }
-            }
-            if (okx) {
-              const long hw = (long)H * W, qq = (long)row * W + x0 + vi;
-              flow_out_r[(long)b * 2 * hw + qq] = tanhf(s0 + s_pw[2 * C32]);
-              flow_out_r[((long)b * 2 + 1) * hw + qq] = tanhf(s1 + s_pw[2 * C32 + 1]);
+              if (rowok && (FULL || x0 + vi < W))
+                flow_out_r[((long)b * 2 + (pub ? 0 : 1)) * ((long)H * W) + (long)row * W + x0 + vi] = tanhf(s + s_pw[2 * C32 + (pub ? 0 : 1)]);
+            } else {
+              // (the PLIF / XLIF / ALIF kernels, at their 168 registers, and the ragged diagonal form gained spills with the split:
+              // both components in the publishing lane, as before)
+              float s0 = 0.f, s1 = 0.f;
+#pragma unroll 1
+              for (int cc = 0; cc < C32; cc += 4) {
+                const float4 pa = *(const float4*)(s_pw + cc), pb4 = *(const float4*)(s_pw + C32 + cc);
+                const float pa4[4] = {pa.x, pa.y, pa.z, pa.w}, pb44[4] = {pb4.x, pb4.y, pb4.z, pb4.w};
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                  const float z = (float)((word >> (cc + q)) & 1u);
+                  s0 += z * pa4[q];
+                  s1 += z * pb44[q];
+                }
+              }
+              if (okx) {
+                const long hw = (long)H * W, qq = (long)row * W + x0 + vi;
+                flow_out_r[(long)b * 2 * hw + qq] = tanhf(s0 + s_pw[2 * C32]);
+                flow_out_r[((long)b * 2 + 1) * hw + qq] = tanhf(s1 + s_pw[2 * C32 + 1]);
+              }
             }
           }
           FT_STAMP();
@@ -853,8 +879,10 @@ int evf_fwd_diag_t_launch(const FwJobs& jobs, int n, int B, int H, int W, void* 
     (void)hipFuncSetAttribute((const void*)k_fwd_diag_t<false, false, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS);
     attr_set = true;
   }
-  // relative cost of a round: feed-forward / recurrent cell / feed-forward cell with the prediction head in team E's epilogue (its
-  // ~320 vector instructions per row make team E the slower team there: 8 k cycles per round against 5.8 k, phase stamps)
+  // relative cost of a round: feed-forward / recurrent cell / feed-forward cell with the prediction head in team E's epilogue
+  // (fitted when the head ran both components in the publishing lanes, ~320 vector instructions per row: 8 k cycles per round
+  // against 5.8 k, phase stamps; with one component per lane the chain launch of that layer costs what a plain layer's does,
+  // and the re-sweep of w_pred found no setting outside the noise: DESIGN section 8)
   // (EVF_FT_W=ff,rec,pred: measurements)
   static int w_ff = 0, w_rec = 0, w_pred = 0;
   if (!w_ff) {
