@@ -90,6 +90,10 @@ NETWORK_SIGNATURES = {
     "evf_head_lif_bwd_wgrad_slabs": [I, I, I],
     "evf_head_lif_bwd_wgrad": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P, P, P, P, P, I, P],
     "evf_head_plif_bwd_wgrad": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P, P, P, P, I, P, P, P, P, P, P, P, P, P],
+    # the head cell's backward in the epilogue of the input-gradient product that makes its dL/d(spikes) (planes, weights first)
+    "evf_head_dgrad_win_fits": [I, I, I, I, I, I, I, I, I],
+    "evf_head_dgrad_win_select": [I, I],
+    "evf_head_bwd_dgrad_win": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P, P, P, P, I, P],
     "evf_sum_rows": [P, I, I, I, P, P],
     "evf_add_segments": [P, P, P, P, I, I, P],
     "evf_pack_conv_weights_b3_multi": [P, P, P, I, P],
@@ -412,7 +416,7 @@ _DEFER_SAFE_FWD = {"evf_conv_lif_fwd_b3", "evf_conv_lif_fwd_b3_pred", "evf_head_
 # backward recording (evf_bwd_defer_*): these record themselves, or flush inside the library when they cannot
 _DEFER_SAFE_BWD = {"evf_lif_bwd_wgrad", "evf_lif_bwd_wgrad2", "evf_lif_bwd_wgrad_top", "evf_plif_bwd_wgrad2", "evf_plif_bwd_wgrad_top", "evf_conv_dgrad_b3_f32",
                    "evf_conv_dgrad_b3_f32_pair", "evf_conv_dgrad_b3", "evf_conv_dgrad_b3_pair", "evf_head_lif_bwd_wgrad", "evf_head_plif_bwd_wgrad",
-                   "evf_bwd_defer_flush"}
+                   "evf_head_bwd_dgrad_win", "evf_bwd_defer_flush"}
 
 
 def zero_(t):

@@ -225,6 +225,24 @@ int evf_dgrad_diag_dma_launch(const EvfDgProds& P, int nprod, int B, int H, int 
 // table of products, 32-bit plane offsets); a cell that does not fit launches directly instead of failing at the flush
 bool evf_dgrad_diag_fits(int split, int B, int H, int W);
 
+// evf_head_dgrad.hip: the head layer's backward of up to 16 consecutive passes in the epilogue of its input-gradient products
+// (k_dgrad_head_win).  Index s = 0 .. np-1 is the backward order (s = 0: the last pass of the group).
+#define EVF_HDW_MAX_P 16
+struct EvfHdwArgs {
+  const void* g[EVF_HDW_MAX_P];          // the three bf16 planes [term][B,H,W,32] of dL/d(current) of the layer above, per pass
+  const float* v_prev[EVF_HDW_MAX_P];    // potential before the pass (NULL: the zero state)
+  const uint32_t* z_prev[EVF_HDW_MAX_P]; // spike words before the pass (NULL: none)
+  const float* x_in[EVF_HDW_MAX_P];      // the network input of the pass [B,Cin,H,W]
+  const void* wt;                        // split transposed feed-forward weights of the layer above (evf_pack_conv_weight_b3t)
+  const float *v_out0, *g_v_out0;        // pass 0: potential behind it, dL/dv carried into it (NULL: none)
+  float* g_v_prev;                       // dL/dv leaving pass np - 1 (NULL: not stored)
+  const float *leak, *thresh;
+  float *g_leak, *g_thresh, *slab;
+  int np, B, Cin, H, W, row_ld, slab_acc, nrows;  // nrows: rows of the slab (evf_head_lif_bwd_wgrad_slabs)
+  float width;
+};
+int evf_head_dgrad_win_launch(const EvfHdwArgs& A, void* stream);
+
 // Deferred backward cells (evf_bwd_defer_*, owner: evf_bwd_fused.hip): while `active`, the fused backward, the fp32 input
 // gradient and the head backward of the default-neuron FireNet path RECORD their launch under index `slot`; the flush
 // launches index after index -- the fused-backward cells of an index as one k_bwd_diag, the input-gradient cells as one

@@ -1657,8 +1657,29 @@ struct HdArgs {
   // PLIF head (evf_head_plif_bwd_wgrad): P != NULL
   const float *g_pt_out, *pt_prev, *P, *leak_pt, *add_pt;
   float *g_pt_prev, *g_leak_pt, *g_add_pt;
+  // evf_head_bwd_dgrad_win: g_z_out is NULL; dL/d(spikes) is the product of these planes of the layer above and its weights
+  const void *gs, *wt;
 };
+// jobs[0 .. m-1]: consecutive passes of a window that carry their product (gs): one k_dgrad_head_win launch
+static int head_dgrad_win_go(const HdArgs* const* jobs, int m, void* stream) {
+  const HdArgs& f = *jobs[0];
+  EvfHdwArgs A;
+  for (int t = 0; t < EVF_HDW_MAX_P; ++t) {
+    const HdArgs& q = *jobs[t < m ? t : 0];
+    A.g[t] = q.gs, A.v_prev[t] = q.v_prev, A.z_prev[t] = q.z_prev, A.x_in[t] = q.x_in;
+  }
+  A.wt = f.wt, A.v_out0 = f.v_out, A.g_v_out0 = f.g_v_out, A.g_v_prev = jobs[m - 1]->g_v_prev;
+  A.leak = f.leak, A.thresh = f.thresh, A.g_leak = f.g_leak, A.g_thresh = f.g_thresh, A.slab = f.slab;
+  A.np = m, A.B = f.B, A.Cin = f.Cin, A.H = f.H, A.W = f.W, A.row_ld = f.accumulate >> 8, A.slab_acc = f.accumulate & 1;
+  A.nrows = evf_head_lif_bwd_wgrad_slabs(f.B, f.H, f.W);
+  A.width = f.act_width;
+  return evf_head_dgrad_win_launch(A, stream);
+}
 static int head_bwd_go(const HdArgs& a, void* stream) {
+  if (a.gs) {
+    const HdArgs* one[1] = {&a};
+    return head_dgrad_win_go(one, 1, stream);
+  }
   const long npix = (long)a.B * a.H * a.W;
   const int nblk = evf_head_lif_bwd_wgrad_slabs(a.B, a.H, a.W);
   const int row_ld = a.accumulate >> 8;  // pitch of the per-block parameter-gradient rows (0: dense outputs, atomics)
@@ -1720,7 +1741,7 @@ int evf_hd_defer_window_ok(int ctx) {
   int ns = 0, n = 0;
   for (int d = 0; d < EVF_BWD_DIAGS; ++d)
     for (int k = 0; k < hd.n[d]; ++k, ++n) {
-      const float* g = hd.job[d][k].g_z_out;
+      const float* g = hd.job[d][k].gs ? (const float*)hd.job[d][k].gs : hd.job[d][k].g_z_out;  // (gs: split planes, one buffer per pass)
       if (!g) continue;
       for (int i = 0; i < ns; ++i)
         if (seen[i] == g) return 0;
@@ -1748,6 +1769,7 @@ int evf_hd_defer_launch_window(int ctx, void* stream) {
             (q.accumulate >> 8) == (p.accumulate >> 8)))
         break;
       if ((q.P != nullptr) != (p.P != nullptr)) break;
+      if ((q.gs != nullptr) != (p.gs != nullptr) || q.wt != p.wt) break;
       if (q.P && !(q.g_pt_out == p.g_pt_prev && q.leak_pt == p.leak_pt && q.add_pt == p.add_pt && q.g_leak_pt == p.g_leak_pt &&
                    q.g_add_pt == p.g_add_pt))
         break;
@@ -1756,6 +1778,8 @@ int evf_hd_defer_launch_window(int ctx, void* stream) {
     evf_prof_mark(m == 1 ? 3 : 5, 0, stream);
     if (m == 1) {
       rc = head_bwd_go(f, stream);
+    } else if (f.gs) {  // the passes' products and the head cell's backward in one launch (evf_head_dgrad.hip)
+      rc = head_dgrad_win_go(jobs + k, m, stream);
     } else {
       HeadBwdWin a;
       for (int t = 0; t < HEADBWD_MAX_P; ++t) {
@@ -1843,10 +1867,28 @@ extern "C" int evf_head_lif_bwd_wgrad(const float* g_z_out, const float* g_v_out
                                       float* g_cur, float* g_v_prev, float* g_leak, float* g_thresh, float* slab,
                                       int accumulate, void* stream) {
   if (!v_out || !x_in || !leak || !thresh || !g_v_prev || !g_leak || !g_thresh || !slab || B <= 0 || H <= 0 || W <= 0 ||
-      Cin != 2)
+      Cin < 1 || Cin > 3)  // (9 Cin <= 32 columns of the weight-gradient product, head_bwd_pass)
     return EVF_EINVAL;
   const HdArgs a{g_z_out, g_v_out, v_out, v_prev, z_prev, x_in, leak, thresh, B, Cin, H, W, hard_reset, surrogate, act_width,
                  g_cur, g_v_prev, g_leak, g_thresh, slab, accumulate, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  return head_bwd_record_or_go(a, stream);
+}
+
+// evf_head_lif_bwd_wgrad with dL/d(spikes) given as the input-gradient product that makes it: g_split = the three bf16 planes of
+// dL/d(current) of the layer above, wT_b3 its split transposed feed-forward weights (include/evflow.h).  Recordable; the recorded
+// cells of a window run in ONE launch (k_dgrad_head_win), a single cell as a launch of one pass.
+extern "C" int evf_head_bwd_dgrad_win(const void* g_split, const void* wT_b3, const float* g_v_out, const float* v_out,
+                                      const float* v_prev, const uint32_t* z_prev, const float* x_in, const float* leak,
+                                      const float* thresh, int B, int Cin, int H, int W, int hard_reset, int surrogate,
+                                      float act_width, float* g_v_prev, float* g_leak, float* g_thresh, float* slab, int accumulate,
+                                      void* stream) {
+  if (!g_split || !wT_b3 || !v_out || !x_in || !leak || !thresh || !g_v_prev || !g_leak || !g_thresh || !slab || B <= 0 ||
+      H <= 0 || W <= 0)
+    return EVF_EINVAL;
+  if (!evf_head_dgrad_win_fits(B, Cin, H, W, hard_reset, surrogate, 1, 1, 0)) return EVF_ENOTSUP;
+  HdArgs a{nullptr, g_v_out, v_out, v_prev, z_prev, x_in, leak, thresh, B, Cin, H, W, hard_reset, surrogate, act_width,
+           nullptr, g_v_prev, g_leak, g_thresh, slab, accumulate, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+           g_split, wT_b3};
   return head_bwd_record_or_go(a, stream);
 }
 

@@ -109,6 +109,10 @@ class _Window:
         self.gcl = [None] * n_  # per-layer g_cur buffers (diagonal backward launches: several layers in flight)
         self.gsl = [None] * n_  # ... or per-layer split planes [3,B,H,W,32] bf16 (SPLIT_DGRAD)
         self.gz0 = []           # dL/d(spikes) of the head layer, one buffer per backward pass (HEAD_WIN)
+        # ... or, when the head's backward runs in the epilogue of the product that makes them (evf_head_bwd_dgrad_win): layer 1's split
+        # planes of every backward pass, kept until the flush; gs0 = the planes of the pass being recorded, for the head cell below
+        self.gsl1 = []
+        self.gs0 = None
         self.bwd_k = 0          # backward passes of this window so far
         self.lm = []            # PLIF_LAYER_MAJOR: (tape, dL/dflow, is_first) of the passes whose backward waits for the window's first
         self.slab_init = {}
@@ -899,6 +903,14 @@ class FireNetEngine:
         plif_hw = (self._plif and HEAD_WIN and PLIF_TRACE_FUSED and self.__dict__.get("_bdefer_on", False)
                    and self.precision == "bf16x3" and n > 1 and tape["x_in"].shape[1] == 2
                    and (self.cells[0].hard_reset or self._xsoft) and self.cells[0].activation == "arctanspike" and (top_fused or g_flow is None))
+        # the head layer's backward in the EPILOGUE of the product that makes its dL/d(spikes) (csrc/evf_head_dgrad.hip): layer 1's
+        # feed-forward input gradient is then not recorded on the diagonals (its recurrent one stays, as a single product), layer 1's
+        # split planes get a buffer per pass, kept until the flush, and win.gz0 is not used.  The library's predicate decides
+        # (LIF head with the default neuron, full tiles, not the deterministic mode, EVF_HEAD_DGRAD_WIN); anything else: the path above
+        c0 = self.cells[0]
+        hdw = bool(bdefer and SPLIT_DGRAD and HEAD_WIN and n > 1 and not self._plif
+                   and _lib.load().evf_head_dgrad_win_fits(B, 2, H, W, 1 if c0.hard_reset else 0, SURROGATE_ID[c0.activation], 1, 1,
+                                                           1 if tape.get("det") else 0) == 1)
         if plif_hw:
             self._bdefer_slot(win, 0)
             if _lib.raw("evf_bwd_defer_hold_heads", 1) != 0:
@@ -918,13 +930,23 @@ class FireNetEngine:
             g_z = win.gz[i] if win.gz_has[i] else None
             g_z2 = win.gzr[i] if win.gzr_has[i] else None  # from the cell's own recurrent input gradient (pass t + 1)
             g_v = win.gv[i]
+            hdw_i = hdw and i == 1 and not win.gz_has[0]  # (this pass's product W_ff^T g_cur goes to the head cell's launch)
+            hd_gs = None  # head cell: the planes that product starts from
+            if i == 0:
+                hd_gs, win.gs0 = win.gs0, None
             win.gz_has[i] = win.gzr_has[i] = False
             top = top_fused and i == n - 1
-            if g_z is None and g_z2 is None and g_v is None and not top:
+            if g_z is None and g_z2 is None and g_v is None and not top and hd_gs is None:
                 continue  # no gradient reaches this layer at this pass
             use_rec = c.recurrent and z_prev is not None
             split = bdefer and SPLIT_DGRAD and i > 0
-            if split:  # the fused backward writes the three bf16 planes of g_cur instead of the fp32 tensor
+            if split and hdw_i:  # ... into a buffer of this pass's own (read after the last diagonal)
+                # (persistent scratch of the engine, one buffer per backward pass: allocated by the warm-up windows, never inside a
+                #  capture; a window's flush precedes the next window's backward in stream order)
+                while len(win.gsl1) <= win.bwd_k:
+                    win.gsl1.append(self._lm_buf(("gsl1", len(win.gsl1)), (3, B, H, W, C), dev, torch.bfloat16))
+                g_cur_i, g_split_i = None, win.gsl1[win.bwd_k]
+            elif split:  # the fused backward writes the three bf16 planes of g_cur instead of the fp32 tensor
                 if win.gsl[i] is None:
                     win.gsl[i] = torch.empty((3, B, H, W, C), dtype=torch.bfloat16, device=dev)
                 g_cur_i, g_split_i = None, win.gsl[i]
@@ -1017,6 +1039,14 @@ class FireNetEngine:
                               _lib.ptr(self._rowed(win, "0.leak_pt")[0]), _lib.ptr(self._rowed(win, "0.add_pt")[0]))
                     win.gpt_has[0] = not is_first
                     trace_fused = True  # (no evf_plif_trace_bwd below)
+                elif hd_gs is not None:  # dL/d(spikes) = W_ff(layer 1)^T g_cur(layer 1), formed inside the launch (k_dgrad_head_win)
+                    if g_z is not None:
+                        raise _lib.EvflowError("head layer: a stored dL/d(spikes) beside the product that replaces it")
+                    _lib.call("evf_head_bwd_dgrad_win", _lib.ptr(hd_gs), _lib.ptr(self._packed[(1, "ff", "b3t")]), _lib.ptr(g_v),
+                              _lib.ptr(v_out), _lib.ptr(v_prev), _lib.ptr(z_prev), _lib.ptr(tape["x_in"]), _lib.ptr(self._flat["0.leak"]),
+                              _lib.ptr(self._flat["0.thresh"]), B, 2, H, W, 1, SURROGATE_ID[c.activation], self._act_width(0),
+                              _lib.ptr(gv_out), _lib.ptr(leak_r), _lib.ptr(thr_r), _lib.ptr(self._slabs[key]),
+                              (1 if win.slab_init.get(key) else 0) | (row_ld << 8))
                 else:
                     _lib.call("evf_head_lif_bwd_wgrad", _lib.ptr(g_z), _lib.ptr(g_v), _lib.ptr(v_out), _lib.ptr(v_prev),
                               _lib.ptr(z_prev), _lib.ptr(tape["x_in"]), _lib.ptr(self._flat["0.leak"]),
@@ -1079,6 +1109,13 @@ class FireNetEngine:
             if i > 0:
                 if bdefer:
                     self._bdefer_slot(win, 2 * (n - 1 - i) + 1)
+                if hdw_i and split:
+                    win.gs0 = g_split_i  # (the head cell of this pass takes the feed-forward product from here)
+                    if rec_grad:  # the recurrent product alone, to the cell's own buffer as in the pair form below
+                        _lib.call("evf_conv_dgrad_b3", _lib.ptr(g_split_i), _lib.ptr(self._packed[(i, "rec", "b3t")]),
+                                  _lib.ptr(win.buf(win.gzr, i)), 0, B, H, W, None, None)
+                        win.gzr_has[i] = True
+                    continue
                 if (bdefer or plif_hw) and i == 1 and HEAD_WIN and not win.gz_has[0]:
                     # dL/d(spikes) of the head layer in a buffer of this pass's own: the head's backward cells of the whole window
                     # then run after the last diagonal, all passes in one launch (evf_hd_defer_launch_window)

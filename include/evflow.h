@@ -597,13 +597,33 @@ int evf_reduce_slabs_multi(const void* const* partial, void* const* dst, int cou
 /* Head layer, neuron backward + weight gradient fused (one pass over the gradient tensors):
  * evf_lif_bwd plus dW partials per block into slab [evf_head_lif_bwd_wgrad_slabs(B,H,W)][32*Cin*9]
  * (torch layout [32][Cin][3][3]; accumulate = 1 adds to the slab), reduced once per window with
- * evf_sum_rows.  x_in [B,Cin,H,W] = the network input, Cin = 2.  g_cur may be null. */
+ * evf_sum_rows.  x_in [B,Cin,H,W] = the network input, Cin <= 3.  g_cur may be null. */
 int evf_head_lif_bwd_wgrad_slabs(int B, int H, int W);
 int evf_head_lif_bwd_wgrad(const float* g_z_out, const float* g_v_out, const float* v_out,
                            const float* v_prev, const uint32_t* z_prev, const float* x_in, const float* leak,
                            const float* thresh, int B, int Cin, int H, int W, int hard_reset, int surrogate,
                            float act_width, float* g_cur, float* g_v_prev, float* g_leak, float* g_thresh,
                            float* slab, int accumulate, void* stream);
+/* evf_head_lif_bwd_wgrad with dL/d(spikes) given as the input-gradient product that makes it (k_dgrad_head_win): g_split = the
+ * three bf16 planes of dL/d(current) of the layer above, wT_b3 its split transposed feed-forward weights
+ * (evf_pack_conv_weight_b3t) -- g_z_out = conv^T(g_split, wT_b3) as evf_conv_dgrad_b3 forms it, never stored.  The head cell's
+ * backward runs in the product's epilogue; the recorded cells of a window (evf_bwd_defer_*; one plane buffer per pass, kept
+ * until the flush) run in ONE launch, tile by tile with the passes of a tile back to back, dL/dv and the potential carried in
+ * registers.  g_v_prev is bit-identical to evf_conv_dgrad_b3 + evf_head_lif_bwd_wgrad; slab and the per-channel rows are the
+ * same sums grouped differently (one row per block, fewer blocks: accumulate = 0 zeroes the slab rows no block owns).
+ * evf_head_dgrad_win_fits: 1 when the path serves the cell -- hard_reset == 1 and the arctan surrogate, Cin <= 3, H % 4 == 0,
+ * W % 32 == 0 and a shape the persistent input-gradient launch takes, pre-split planes, one plane buffer per pass, not the
+ * deterministic mode, and not switched off (environment EVF_HEAD_DGRAD_WIN=0); else 0, and the entry point returns
+ * EVF_ENOTSUP.  evf_head_dgrad_win_select(on, blocks): on = -1 environment / default, 0 off, 1 on; blocks = 0 default grid
+ * (one block per CU; environment EVF_HEAD_DGRAD_BLOCKS), else the grid (capped at the slab's rows).  Process-wide. */
+int evf_head_dgrad_win_fits(int B, int Cin, int H, int W, int hard_reset, int surrogate, int split_planes,
+                            int planes_per_pass, int deterministic);
+int evf_head_dgrad_win_select(int on, int blocks);
+int evf_head_bwd_dgrad_win(const void* g_split, const void* wT_b3, const float* g_v_out, const float* v_out,
+                           const float* v_prev, const uint32_t* z_prev, const float* x_in, const float* leak,
+                           const float* thresh, int B, int Cin, int H, int W, int hard_reset, int surrogate,
+                           float act_width, float* g_v_prev, float* g_leak, float* g_thresh, float* slab,
+                           int accumulate, void* stream);
 /* PLIF head (reference models/spiking_submodules.py:191-227, backward of :634-652): evf_head_lif_bwd_wgrad with the presynaptic
  * trace's backward in the same pass -- what evf_plif_trace_bwd computes from g_cur in a launch of its own (g_cur is not written;
  * the head's input is the event tensor, so dL/d(pooled activity) is not needed): g_pt_prev (may alias g_pt_carry) and the sums for
