@@ -173,7 +173,7 @@ extern "C" int evf_chan_affine(const float* g, int ldg, const float* x, int ldx,
 // Weight normalisation of a conv weight (norm = "weight" cells, spiking_submodules.py:87-88, :502-504: nn.utils.weight_norm,
 // dim = 0):  w[o, :] = v[o, :] * g[o] / ||v[o, :]||, the norm over the n = Cin * k * k elements of an output channel.
 // One block per output channel; the norms are kept for the backward:
-//   d v[o, j] = (g / nrm) * gw[o, j] - (g * <gw[o], v[o]> / nrm^3) * v[o, j],    d g[o] = <gw[o], v[o]> / nrm
+//   d v[o, j] = (g / nrm) * (gw[o, j] - v[o, j] * <gw[o], v[o]> / nrm^2),    d g[o] = <gw[o], v[o]> / nrm
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float wn_block_sum(float s, float* s_red) {
 #pragma unroll
@@ -210,8 +210,10 @@ __global__ __launch_bounds__(256) void k_weight_norm_bwd(const float* __restrict
   float s = 0.f;
   for (int j = threadIdx.x; j < n; j += blockDim.x) s += gw[o * n + j] * v[o * n + j];
   const float dot = wn_block_sum(s, s_red);
-  const float nr = nrm[o], a = g[o] / nr, b = g[o] * dot / (nr * nr * nr);
-  for (int j = threadIdx.x; j < n; j += blockDim.x) gv[o * n + j] = a * gw[o * n + j] - b * v[o * n + j];
+  // (g / nrm) (gw - v <gw, v> / nrm^2), the form of ATen's weight_norm backward: nrm^2 is a normal float wherever the forward's sum of
+  // squares was one, while nrm^3 underflows to 0 (b = inf) for rows of magnitude 1e-18 and overflows (b = 0) for rows of 1e+18
+  const float nr = nrm[o], a = g[o] / nr, q = dot / (nr * nr);
+  for (int j = threadIdx.x; j < n; j += blockDim.x) gv[o * n + j] = a * (gw[o * n + j] - v[o * n + j] * q);
   if (threadIdx.x == 0) gg[o] = dot / nr;
 }
 
