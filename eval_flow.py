@@ -63,6 +63,10 @@ def test(args, config_parser):
         from event_flow_amd.dataloader.synthetic_loader import SyntheticLoader
 
         data = SyntheticLoader(config, config["model"]["num_bins"], device=device, num_sequences=args.sequences)
+    elif getattr(args, "resident", False):  # the sequence files uploaded once, every batch cut and filtered on the GPU
+        from event_flow_amd.dataloader.resident import ResidentLoader
+
+        data = ResidentLoader(config, config["model"]["num_bins"], device=device)
     else:
         from event_flow_amd.dataloader.h5 import H5Loader
 
@@ -133,6 +137,8 @@ if __name__ == "__main__":
     parser.add_argument("--weights", default="", help="state_dict (reference: the run id)")
     parser.add_argument("--synthetic", action="store_true")
     parser.add_argument("--sequences", type=int, default=4)
+    parser.add_argument("--resident", action="store_true",
+                        help="keep the sequence files in device memory and cut the input windows there (data.mode events)")
     parser.add_argument("--store", default="", help="directory that receives results/eval_0/<sequence>/{events,flow,iwe,...}/*.png")
     args = parser.parse_args()
     test(args, YAMLParser(args.config))

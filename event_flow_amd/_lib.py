@@ -51,6 +51,9 @@ SIGNATURES = {
     "evf_aee": [P, P, P, P, I, I, I, F, P, P],
     "evf_mask_union": [P, I, I, I, I, P, P],
     "evf_masked_flow_mean": [P, P, I, I, I, I, P, P],
+    # device-resident sequences (dataloader/resident.py): arena columns, total, first, flags, B, P, N, H, W, ev, dt_input
+    "evf_seq_cut": [P, P, P, P, L, P, P, I, I, I, I, I, P, P, P],
+    "evf_hot_pixels": [P, P, P, P, P, P, I, I, I, I, I, I, I, F, P],
 }
 
 # network entry points (added as the kernels land)

@@ -692,6 +692,28 @@ int evf_nchw_to_nhwc(const float* in, int B, int C, int H, int W, float* out, vo
  * x [B,C,H,W] *= mask [B,H,W] (one binary mask per batch slot, dataloader/base.py:224-243). */
 int evf_apply_pixel_mask(float* x, const float* mask, int B, int C, int H, int W, void* stream);
 
+/* ------------------------------------------------------------------ device-resident sequences
+ * (dataloader/resident.py, csrc/evf_resident.hip): the sequence files of a loader live in device memory as one arena per
+ * column -- xs, ys uint16, ts float64 relative to its file's t0, ps uint8 in {0,1}, `total` events in all.
+ *
+ * evf_seq_cut: job j = b * P + p takes the N events from arena index first[j] on (int64 [B*P], device memory) and writes
+ * them as float32 rows (t, y, x, p) to ev [B][P][N][4] -- event_formatting + augment_events (dataloader/base.py:60-83):
+ * t = (t32 - t32_first) / (t32_last - t32_first) in float32, p = 2p - 1, and with flags[j] (int32, device memory) bit 0
+ * x = W-1-x, bit 1 y = H-1-y, bit 2 p = -p.  dt_input [P][B] float64 = ts[last] - ts[first].  A job that does not lie
+ * inside the arena gives padding rows (p = 0) and dt_input 0.  B * P <= 65535. */
+int evf_seq_cut(const uint16_t* xs, const uint16_t* ys, const double* ts, const uint8_t* ps, int64_t total,
+                const int64_t* first, const int* flags, int B, int P, int N, int H, int W, float* ev, double* dt_input,
+                void* stream);
+/* evf_hot_pixels: create_hot_mask + get_hot_event_mask (dataloader/base.py:224-243, encodings.py:88-103) for the P passes
+ * ev [B][P][N][4] of B slots, in pass order.  events [B][H][W] int32 and obvs [B] int32 are the slots' persistent statistics
+ * (read and updated); reset [B][P] int32 != 0 zeroes a slot's statistics before that pass.  Per pass: every pixel with an
+ * event (p != 0) counts once, obvs += 1, and if obvs > min_obvs the mask clears the pixels whose rate events / obvs
+ * (float32) exceeds max_rate -- at most max_px, highest rate first, the lowest flat index among equal rates.
+ * Masks (1 keep, 0 hot): mask_bp [B][P][H][W] and / or mask_pb [P][B][H][W] (either may be NULL, not both).
+ * max_rate >= 0, H * W <= 2^18.  No atomics on global memory: a slot belongs to one block. */
+int evf_hot_pixels(const float* ev, const int* reset, int* events, int* obvs, float* mask_bp, float* mask_pb, int B, int P,
+                   int N, int H, int W, int max_px, int min_obvs, float max_rate, void* stream);
+
 /* Window masks: out [B,1,H,W] = min(sum_p masks[B,P,H,W], 1) (loss/flow.py:149-150); masked mean of the
  * per-pass flow maps [B,P,2,H,W] -> [B,2,H,W], sum_p maps*mask / (sum_p mask + 1e-9) (loss/flow.py:443-452). */
 int evf_mask_union(const float* masks, int B, int P, int H, int W, float* out, void* stream);

@@ -53,6 +53,11 @@ def train(args, config_parser):
 
         data = SyntheticLoader(config, config["model"]["num_bins"], config["model"].get("round_encoding", False), device=device,
                                seed_offset=1000 * rank)
+    elif getattr(args, "resident", False):  # the sequence files uploaded once, every batch cut and filtered on the GPU
+        from event_flow_amd.dataloader.resident import ResidentLoader
+
+        data = ResidentLoader(config, config["model"]["num_bins"], config["model"].get("round_encoding", False), device=device,
+                              rank=rank, world_size=world)
     else:
         from event_flow_amd.dataloader.h5 import H5Loader
 
@@ -152,5 +157,7 @@ if __name__ == "__main__":
     parser.add_argument("--out", default="", help="where to save the best state_dict")
     parser.add_argument("--epochs", type=int, default=None)
     parser.add_argument("--fused-optimizer", action="store_true")
+    parser.add_argument("--resident", action="store_true",
+                        help="keep the sequence files in device memory and cut the input windows there (data.mode events)")
     args = parser.parse_args()
     train(args, YAMLParser(args.config))
