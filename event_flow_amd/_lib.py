@@ -54,6 +54,8 @@ SIGNATURES = {
     # device-resident sequences (dataloader/resident.py): arena columns, total, first, flags, B, P, N, H, W, ev, dt_input
     "evf_seq_cut": [P, P, P, P, L, P, P, I, I, I, I, I, P, P, P],
     "evf_hot_pixels": [P, P, P, P, P, P, I, I, I, I, I, I, I, F, P],
+    # conditional zero-fill of up to 32 segments: device flag (or NULL), host arrays dst / bytes (int64), nseg
+    "evf_zero_segments_if": [P, P, P, I, P],
 }
 
 # network entry points (added as the kernels land)

@@ -4,8 +4,9 @@
 //   evf_seq_cut     input windows cut out of the sequence columns that were uploaded once, formatted and flipped like
 //                   event_formatting / augment_events, one 16-byte row (t, y, x, p) per event.
 //   evf_hot_pixels  create_hot_mask + get_hot_event_mask: the persistent per-slot statistics and the mask of every pass.
+//   evf_zero_segments_if  the recurrent state's reset as a node of a replayed step: zero-fill under a device flag.
 //
-// Both are plain streaming kernels: a c3 window is 80 jobs x 1000 events (1 MB of rows) and 80 masks of 128 x 128 pixels.
+// All are plain streaming kernels: a c3 window is 80 jobs x 1000 events (1 MB of rows) and 80 masks of 128 x 128 pixels.
 // Built with -ffp-contract=off; the float division below is the correctly rounded one, so the normalised timestamps carry
 // numpy's bits.
 #include "evf_common.h"
@@ -182,5 +183,57 @@ extern "C" int evf_hot_pixels(const float* ev, const int* reset, int* events, in
   const size_t lds = sizeof(uint32_t) * (((size_t)H * W + 31) / 32 + 16 + HOT_THREADS);
   hipLaunchKernelGGL(k_hot_pixels, dim3(B), dim3(HOT_THREADS), lds, EVF_STREAM(stream), (const float4*)ev, reset, events, obvs,
                      mask_bp, mask_pb, B, P, N, H, W, max_px, min_obvs, max_rate);
+  return evf_status();
+}
+
+// --------------------------------------------------------------------------
+// evf_zero_segments_if
+// --------------------------------------------------------------------------
+// Up to 32 segments (4-byte aligned, a multiple of 4 bytes long) set to zero bytes when *flag != 0 (flag NULL: always); block y =
+// segment, a grid-stride loop of 16-byte stores over the segment's 16-byte aligned middle, dword stores for the up to three words
+// before and after it.  A block whose flag reads 0 returns before any store: the clear case is one empty launch.
+#define ZERO_THREADS 256
+#define ZERO_MAX_BLOCKS 512  // per segment: one sweep of the grid covers 2 MiB of it
+struct ZeroSegs {
+  uint32_t* dst[32];
+  long long bytes[32];
+};
+__global__ void __launch_bounds__(ZERO_THREADS) k_zero_segments_if(const int* __restrict__ flag, ZeroSegs sg) {
+  __shared__ int go;
+  if (threadIdx.x == 0) go = flag ? *flag : 1;  // one load per block
+  __syncthreads();
+  if (go == 0) return;
+  const int k = blockIdx.y;
+  uint32_t* p = sg.dst[k];
+  const long words = sg.bytes[k] >> 2;
+  long head = (long)(((16u - (uint32_t)((uintptr_t)p & 15u)) & 15u) >> 2);  // words in front of the first 16-byte boundary
+  if (head > words) head = words;
+  const long nvec = (words - head) >> 2;
+  const long tail0 = head + 4 * nvec;  // first word behind the last whole vector
+  uint4* v = (uint4*)(p + head);
+  const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+  for (long i = (long)blockIdx.x * ZERO_THREADS + threadIdx.x; i < nvec; i += (long)gridDim.x * ZERO_THREADS) v[i] = z;
+  if (blockIdx.x == 0) {
+    if ((long)threadIdx.x < head) p[threadIdx.x] = 0u;
+    if (tail0 + (long)threadIdx.x < words) p[tail0 + threadIdx.x] = 0u;  // (at most three words)
+  }
+}
+
+extern "C" int evf_zero_segments_if(const int* flag, void* const* dst, const int64_t* bytes, int nseg, void* stream) {
+  if (!dst || !bytes || nseg < 1 || nseg > 32) return EVF_EINVAL;
+  ZeroSegs sg;
+  long long most = 0;
+  for (int k = 0; k < 32; ++k) {
+    sg.dst[k] = nullptr;
+    sg.bytes[k] = 0;
+    if (k >= nseg) continue;
+    if (!dst[k] || ((uintptr_t)dst[k] & 3u) || bytes[k] < 0 || (bytes[k] & 3)) return EVF_EINVAL;
+    sg.dst[k] = (uint32_t*)dst[k];
+    sg.bytes[k] = (long long)bytes[k];
+    if (sg.bytes[k] > most) most = sg.bytes[k];
+  }
+  int blocks = evf_cdiv((long)most, (long)ZERO_THREADS * 16);
+  blocks = blocks < 1 ? 1 : (blocks > ZERO_MAX_BLOCKS ? ZERO_MAX_BLOCKS : blocks);
+  hipLaunchKernelGGL(k_zero_segments_if, dim3(blocks, nseg), dim3(ZERO_THREADS), 0, EVF_STREAM(stream), flag, sg);
   return evf_status();
 }

@@ -106,6 +106,21 @@ class ResidentPlan(H5Loader):
             group.append((jobs, restarted, done))
         return discarded, group, reset
 
+    def plan_steps(self, P, n_epochs):
+        """The optimizer steps of `n_epochs` passes over the files, as train_flow.py's loop takes them: (discarded, group,
+        reset, epoch) per step, `plan_window`'s triple and the pass the step belongs to.  A batch belongs to pass e when e
+        wrap-around (`done`) batches were delivered strictly before it, a step to the pass of its group's last batch; the
+        generator ends before the first step whose last batch lies in pass `n_epochs` (a partial group at the end is not
+        stepped)."""
+        wraps = 0  # `done` batches delivered so far
+        while True:
+            discarded, group, reset = self.plan_window(P)
+            epoch = wraps + sum(1 for _j, _r, done in discarded + group[:-1] if done)
+            if epoch >= n_epochs:
+                return
+            yield discarded, group, reset, epoch
+            wraps = epoch + (1 if group[-1][2] else 0)
+
 
 class ResidentLoader(ResidentPlan):
     def __init__(self, config, num_bins, round_encoding=False, device=None, rank=0, world_size=1):
@@ -153,37 +168,65 @@ class ResidentLoader(ResidentPlan):
         return lengths
 
     # ------------------------------------------------------------------ launches
+    def _job_table(self, batches):
+        """The host table of P planned batches, job j = b * P + p: `first` int64 [B*P], then as int32 `flags` [B*P] | slot
+        `reset` [B*P] | the window's `reset` (did the first batch restart a slot: train_flow.py's loop reset the model in front
+        of it) -- one int64 array of 2*B*P + 1 words."""
+        B, P, N = self.batch_size, len(batches), self.window
+        tab = np.zeros(2 * B * P + 1, dtype=np.int64)
+        aux = tab[B * P:].view(np.int32)
+        for p, (jobs, _restarted, _done) in enumerate(batches):
+            for b, (path, first, flags, restarted) in enumerate(jobs):
+                tab[b * P + p] = self.offsets[path] + first
+                aux[b * P + p] = flags
+                aux[B * P + b * P + p] = 1 if restarted else 0
+        aux[2 * B * P] = 1 if batches[0][1] else 0
+        self._last_row = int(tab[B * P - 1]) + N - 1  # last event of the last slot's last pass
+        return tab
+
+    def _launch_cut(self, table_dev, P, ev, dt, m_bp=None, m_pb=None):
+        """evf_seq_cut and, with the hot filter, evf_hot_pixels on a job table in device memory (`_job_table`'s layout), into
+        the caller's ev [B,P,N,4], dt [P,B] float64 and masks m_bp [B,P,H,W] / m_pb [P,B,H,W] (either may be None).  No
+        allocation and no host copy: the launches can be captured."""
+        B, N = self.batch_size, self.window
+        H, W = self.res
+        at = table_dev.data_ptr()
+        _lib.call("evf_seq_cut", _lib.ptr(self._xs), _lib.ptr(self._ys), _lib.ptr(self._ts), _lib.ptr(self._ps), self.total_events,
+                  at, at + 8 * B * P, B, P, N, H, W, _lib.ptr(ev), _lib.ptr(dt))
+        if self.hot:
+            hf = self.config["hot_filter"]
+            _lib.call("evf_hot_pixels", _lib.ptr(ev), at + 12 * B * P, _lib.ptr(self._hot_events), _lib.ptr(self._hot_obvs),
+                      _lib.ptr(m_bp), _lib.ptr(m_pb), B, P, N, H, W, int(hf["max_px"]), int(hf["min_obvs"]), float(hf["max_rate"]))
+
     def _cut(self, batches):
         """P planned batches -> ev [B,P,N,4], dt_input [P,B], hot masks ([B,P,H,W], [P,B,H,W]) or None: one copy of the job
         table, one evf_seq_cut, one evf_hot_pixels."""
         B, P, N = self.batch_size, len(batches), self.window
         H, W = self.res
         dev = self.device
-        tab = np.zeros((2, B * P), dtype=np.int64)  # row 0: first (int64); row 1 as int32: flags [B*P] | reset [B*P]
-        aux = tab[1].view(np.int32)
-        for p, (jobs, _restarted, _done) in enumerate(batches):
-            for b, (path, first, flags, restarted) in enumerate(jobs):
-                tab[0, b * P + p] = self.offsets[path] + first
-                aux[b * P + p] = flags
-                aux[B * P + b * P + p] = 1 if restarted else 0
-        self._last_row = int(tab[0, B * P - 1]) + N - 1  # last event of the last slot's last pass
-        t = torch.from_numpy(tab)
+        t = torch.from_numpy(self._job_table(batches))
         t = t.pin_memory().to(dev, non_blocking=True)
-        aux_dev = t[1].view(torch.int32)
         ev = torch.empty((B, P, N, 4), dtype=torch.float32, device=dev)
         dt = torch.empty((P, B), dtype=torch.float64, device=dev)
-        _lib.call("evf_seq_cut", _lib.ptr(self._xs), _lib.ptr(self._ys), _lib.ptr(self._ts), _lib.ptr(self._ps), self.total_events,
-                  t.data_ptr(), aux_dev.data_ptr(), B, P, N, H, W, _lib.ptr(ev), _lib.ptr(dt))
-        masks = None
+        m_bp = m_pb = None
         if self.hot:
-            hf = self.config["hot_filter"]
             m_bp = torch.empty((B, P, H, W), dtype=torch.float32, device=dev)
             m_pb = torch.empty((P, B, H, W), dtype=torch.float32, device=dev) if P > 1 else None  # (P = 1: the same layout)
-            _lib.call("evf_hot_pixels", _lib.ptr(ev), aux_dev.data_ptr() + 4 * B * P, _lib.ptr(self._hot_events),
-                      _lib.ptr(self._hot_obvs), _lib.ptr(m_bp), _lib.ptr(m_pb), B, P, N, H, W, int(hf["max_px"]),
-                      int(hf["min_obvs"]), float(hf["max_rate"]))
-            masks = (m_bp, m_pb if m_pb is not None else m_bp.view(P, B, H, W))
+        self._launch_cut(t, P, ev, dt, m_bp, m_pb)
+        masks = (m_bp, m_pb if m_pb is not None else m_bp.view(P, B, H, W)) if self.hot else None
         return ev, dt, masks
+
+    def _mask_window(self, passes, m_bp, m_pb):
+        """The hot-pixel masks applied in place to the window buffers behind `passes` (encode_window's dicts)."""
+        B, P = self.batch_size, len(passes)
+        H, W = self.res
+        # network inputs are pass-major ([P,B,C,H,W], one tensor per pass), the loss's mask stack batch-major ([B,P,H,W])
+        cnt = torch.as_strided(passes[0]["event_cnt"], (P * B, 2, H, W), passes[0]["event_cnt"].stride())
+        vox = torch.as_strided(passes[0]["event_voxel"], (P * B, self.num_bins, H, W), passes[0]["event_voxel"].stride())
+        emask = torch.as_strided(passes[0]["event_mask"], (B * P, 1, H, W), (H * W, H * W, W, 1))
+        _lib.call("evf_apply_pixel_mask", _lib.ptr(vox), _lib.ptr(m_pb), P * B, self.num_bins, H, W)
+        _lib.call("evf_apply_pixel_mask", _lib.ptr(cnt), _lib.ptr(m_pb), P * B, 2, H, W)
+        _lib.call("evf_apply_pixel_mask", _lib.ptr(emask), _lib.ptr(m_bp), B * P, 1, H, W)
 
     def _produce(self, batch):
         """One planned batch -> the reference's batch dict (dataloader/base.py:248-265)."""
@@ -221,18 +264,10 @@ class ResidentLoader(ResidentPlan):
             for at in range(0, len(discarded), 64):  # statistics only; masks and rows are dropped
                 self._cut(discarded[at:at + 64])
         B = self.batch_size
-        H, W = self.res
         ev, dt, masks = self._cut(group)
         passes = encode_window(ev, self.num_bins, self.res, round_ts=self.round_encoding)
         if masks is not None:
-            m_bp, m_pb = masks
-            # network inputs are pass-major ([P,B,C,H,W], one tensor per pass), the loss's mask stack batch-major ([B,P,H,W])
-            cnt = torch.as_strided(passes[0]["event_cnt"], (P * B, 2, H, W), passes[0]["event_cnt"].stride())
-            vox = torch.as_strided(passes[0]["event_voxel"], (P * B, self.num_bins, H, W), passes[0]["event_voxel"].stride())
-            emask = torch.as_strided(passes[0]["event_mask"], (B * P, 1, H, W), (H * W, H * W, W, 1))
-            _lib.call("evf_apply_pixel_mask", _lib.ptr(vox), _lib.ptr(m_pb), P * B, self.num_bins, H, W)
-            _lib.call("evf_apply_pixel_mask", _lib.ptr(cnt), _lib.ptr(m_pb), P * B, 2, H, W)
-            _lib.call("evf_apply_pixel_mask", _lib.ptr(emask), _lib.ptr(m_bp), B * P, 1, H, W)
+            self._mask_window(passes, *masks)
         zeros = torch.zeros((P, B), dtype=torch.float64, device=self.device)
         for p, d in enumerate(passes):
             d["dt_gt"] = zeros[p]

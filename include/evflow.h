@@ -713,6 +713,13 @@ int evf_seq_cut(const uint16_t* xs, const uint16_t* ys, const double* ts, const 
  * max_rate >= 0, H * W <= 2^18.  No atomics on global memory: a slot belongs to one block. */
 int evf_hot_pixels(const float* ev, const int* reset, int* events, int* obvs, float* mask_bp, float* mask_pb, int B, int P,
                    int N, int H, int W, int max_px, int min_obvs, float max_rate, void* stream);
+/* evf_zero_segments_if: the reset of a recurrent state as a node of a replayed training step (train.ResidentWindowStep).
+ * flag: device int32, read by the kernel; != 0 -> every segment is set to zero bytes, == 0 -> nothing is written.  flag NULL ->
+ * unconditional.  dst / bytes: HOST arrays of nseg <= 32 entries, passed by value in the launch's arguments (the
+ * evf_add_segments convention), so the call allocates nothing, copies nothing and can be captured.  Every dst is 4-byte
+ * aligned, every bytes a multiple of 4 (0 allowed).  EVF_EINVAL: dst or bytes NULL, nseg outside 1..32, a NULL or
+ * misaligned segment, a negative size or one that is no multiple of 4. */
+int evf_zero_segments_if(const int* flag, void* const* dst, const int64_t* bytes, int nseg, void* stream);
 
 /* Window masks: out [B,1,H,W] = min(sum_p masks[B,P,H,W], 1) (loss/flow.py:149-150); masked mean of the
  * per-pass flow maps [B,P,2,H,W] -> [B,2,H,W], sum_p maps*mask / (sum_p mask + 1e-9) (loss/flow.py:443-452). */

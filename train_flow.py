@@ -6,7 +6,8 @@ Differences, all host side: MLflow and the visualiser are optional extras of the
 go to stdout and `--out` receives the checkpoint).  Data: the sequence files under `data.path` (HDF5 through h5py, or
 the `.npz` flavour of the same layout, event_flow_amd/dataloader/h5.py), or `--synthetic` windows (moving dots with
 known motion).  `--fused-optimizer` swaps `clip_grad_norm_` + `torch.optim.Adam` for the fused flat-buffer kernel
-(same update rule).
+(same update rule).  `--resident --graphed --fused-optimizer` replays every optimizer step from a hipGraph that begins at the
+cut out of the device-resident sequences (event_flow_amd.train.ResidentWindowStep).
 
   python train_flow.py --config configs/train_SNN.yml --synthetic [--epochs 5] [--out model.pth]
 """
@@ -26,12 +27,77 @@ from event_flow_amd.train import FlatAdam
 from event_flow_amd.utils.utils import load_model
 
 
-def train(args, config_parser):
+def _graphed_refusal(args):
+    """Why --graphed cannot serve this call (None: it can), from the arguments and the environment alone."""
+    if args.synthetic:
+        return "--graphed replays windows cut out of device-resident sequence files; --synthetic has none"
+    if not getattr(args, "resident", False):
+        return "--graphed needs --resident: the replayed step begins at the cut out of the sequences in device memory"
+    if not args.fused_optimizer:
+        return "--graphed needs --fused-optimizer: the replayed step ends in the flat clip + Adam kernel"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return ("--graphed runs on one rank: the ranks would have to agree on every batch's restart flag while the windows are "
+                "planned; use --resident without --graphed under torch.distributed.run")
+    return None
+
+
+def train_graphed(args, config, model, loss_function, optimizer, data, n_epochs, replay=True):
+    """The epochs of `train` with every optimizer step taken by a ResidentWindowStep: the same steps on the same batches as the
+    loop below (ResidentPlan.plan_steps), per-epoch losses and the best-loss checkpoint by the same arithmetic, closed when the
+    first step of a later epoch arrives and after the last step.  -> (history, best loss, the stepper's counters)."""
+    from event_flow_amd.train import ResidentWindowStep
+
+    P = -(-int(config["data"]["window_loss"]) // int(config["data"]["window"]))  # passes until window_loss events are collected
+    stepper = ResidentWindowStep(model, loss_function, optimizer, data, P, replay=replay)
+    device = data.device
+    best_loss, history = 1.0e6, []
+    t_start = time.time()
+    state = {"loss": torch.zeros((), device=device), "samples": 0, "steps": 0}
+
+    def close_epoch():
+        nonlocal best_loss
+        epoch_loss = float(state["loss"]) / max(state["samples"], 1)
+        history.append(epoch_loss)
+        if config["vis"].get("verbose", False):
+            print("Train Epoch: {:04d}  Loss: {:.6f}  ({} optimizer steps, {:.1f} s)".format(len(history) - 1, epoch_loss,
+                                                                                             state["steps"], time.time() - t_start))
+        if epoch_loss < best_loss:
+            best_loss = epoch_loss
+            if args.out:
+                torch.save(model.state_dict(), args.out)
+        state.update(loss=torch.zeros((), device=device), samples=0, steps=0)
+
+    for discarded, group, reset, epoch in data.plan_steps(P, n_epochs):
+        while len(history) < epoch:
+            close_epoch()
+        loss, _info = stepper.step((discarded, group, reset))
+        with torch.cuda.stream(stepper.stream):  # before the next replay rewrites the graph's loss tensor
+            state["loss"] += loss
+        torch.cuda.current_stream().wait_stream(stepper.stream)
+        state["samples"] += config["loader"]["batch_size"]
+        state["steps"] += 1
+    while len(history) < n_epochs:
+        close_epoch()
+    return history, best_loss, dict(stepper.stats)
+
+
+def train(args, config_parser, graphed_replay=True):
+    """`graphed_replay=False`: with --graphed, every step runs the window's launches eagerly (the A/B of the replay)."""
+    graphed = getattr(args, "graphed", False)
+    if graphed and _graphed_refusal(args):
+        raise SystemExit(_graphed_refusal(args))
     config = config_parser.config
     if config["data"]["mode"] == "frames":
         print("Config error: Training pipeline not compatible with frames mode.")
         raise AttributeError
     config = config_parser.combine_entries(config)
+    model = None
+    if graphed:  # (built on the host first: the refusal comes before any device work)
+        model = MODELS[config["model"]["name"]](config["model"].copy())
+        path, why = getattr(model, "compute_path", ("general", "no FireNet-family network"))
+        if path != "fused":
+            raise SystemExit(f"--graphed replays the fused FireNet engine's step; {config['model']['name']} runs on the general "
+                             f"path ({why}): use --resident without --graphed")
     device = config_parser.device
     if torch.device(device).type == "cuda":
         torch.cuda.set_device(device)  # the evf_* launches go to the current device's stream (loader.gpu may not be 0)
@@ -65,14 +131,14 @@ def train(args, config_parser):
                         rank=rank, world_size=world)
 
     loss_function = EventWarping(config, device)
-    model = MODELS[config["model"]["name"]](config["model"].copy()).to(device)
+    model = (model if model is not None else MODELS[config["model"]["name"]](config["model"].copy())).to(device)
     if args.prev:  # a state_dict file, a reference checkpoint (pickled model) or its MLflow run id under ./mlruns
         model = load_model(args.prev, model, device)
     model.train()
 
     clip = config["loss"].get("clip_grad", None)
     if args.fused_optimizer:
-        optimizer = FlatAdam(model, lr=config["optimizer"]["lr"], clip=clip)
+        optimizer = FlatAdam(model, lr=config["optimizer"]["lr"], clip=clip, device_step=graphed)
     else:
         optimizer = getattr(torch.optim, config["optimizer"]["name"])(model.parameters(), lr=config["optimizer"]["lr"])
     if dp:  # every rank starts from rank 0's parameters
@@ -84,6 +150,11 @@ def train(args, config_parser):
     best_loss, history = 1.0e6, []
     t_start = time.time()
     data.shuffle()  # once, before the first epoch (train_flow.py:92)
+    if graphed:
+        history, best_loss, counters = train_graphed(args, config, model, loss_function, optimizer, data, n_epochs, graphed_replay)
+        print(json.dumps({"model": config["model"]["name"], "epochs": n_epochs, "loss_per_epoch": history, "best_loss": best_loss,
+                          "ranks": world, "graphed": counters}))
+        return history
     for epoch in range(n_epochs):
         train_loss, samples, steps = torch.zeros((), device=device), 0, 0
         batches = iter(data)
@@ -159,5 +230,7 @@ if __name__ == "__main__":
     parser.add_argument("--fused-optimizer", action="store_true")
     parser.add_argument("--resident", action="store_true",
                         help="keep the sequence files in device memory and cut the input windows there (data.mode events)")
+    parser.add_argument("--graphed", action="store_true",
+                        help="with --resident --fused-optimizer: replay every optimizer step, from the cut to clip + Adam, from a hipGraph")
     args = parser.parse_args()
     train(args, YAMLParser(args.config))
