@@ -64,9 +64,12 @@ def test(args, config_parser):
 
         data = SyntheticLoader(config, config["model"]["num_bins"], device=device, num_sequences=args.sequences)
     elif getattr(args, "resident", False):  # the sequence files uploaded once, every batch cut and filtered on the GPU
-        from event_flow_amd.dataloader.resident import ResidentLoader
+        if config["data"]["mode"] == "events":
+            from event_flow_amd.dataloader.resident import ResidentLoader as Resident
+        else:  # windows by time, frame or ground-truth map: borders searched once, ragged batches, resident maps / frames
+            from event_flow_amd.dataloader.resident_eval import ResidentEvalLoader as Resident
 
-        data = ResidentLoader(config, config["model"]["num_bins"], device=device)
+        data = Resident(config, config["model"]["num_bins"], device=device)
     else:
         from event_flow_amd.dataloader.h5 import H5Loader
 
@@ -138,7 +141,9 @@ if __name__ == "__main__":
     parser.add_argument("--synthetic", action="store_true")
     parser.add_argument("--sequences", type=int, default=4)
     parser.add_argument("--resident", action="store_true",
-                        help="keep the sequence files in device memory and cut the input windows there (data.mode events)")
+                        help="keep the sequence files in device memory and cut the input windows there (every data.mode: "
+                             "ResidentLoader for events, ResidentEvalLoader with resident ground-truth maps / frames for time, "
+                             "frames, gtflow_dt1 and gtflow_dt4)")
     parser.add_argument("--store", default="", help="directory that receives results/eval_0/<sequence>/{events,flow,iwe,...}/*.png")
     args = parser.parse_args()
     test(args, YAMLParser(args.config))

@@ -56,6 +56,13 @@ SIGNATURES = {
     "evf_hot_pixels": [P, P, P, P, P, P, I, I, I, I, I, I, I, F, P],
     # conditional zero-fill of up to 32 segments: device flag (or NULL), host arrays dst / bytes (int64), nseg
     "evf_zero_segments_if": [P, P, P, I, P],
+    # device-resident evaluation (dataloader/resident_eval.py): ts, total, seg_begin, seg_len, query, Q, out
+    "evf_ts_search": [P, L, P, P, P, L, P, P],
+    # arena columns, total, first, count, flags, J, Npad, H, W, ev, dt_input
+    "evf_seq_cut_ragged": [P, P, P, P, L, P, P, P, I, I, I, I, P, P, P],
+    # maps, M, idx, flags, B, H, W, out  /  frames, M, curr, next, flags, B, H, W, out
+    "evf_gather_flowmaps": [P, I, P, P, I, I, I, P, P],
+    "evf_gather_frames": [P, I, P, P, P, I, I, I, P, P],
 }
 
 # network entry points (added as the kernels land)

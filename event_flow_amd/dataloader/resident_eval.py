@@ -1,0 +1,388 @@
+"""Device-resident evaluation: `data.mode` `time`, `frames`, `gtflow_dt1` and `gtflow_dt4` on sequence files that are uploaded
+ONCE -- the modes the reference evaluates with (AEE needs the ground-truth modes).  Every batch is cut, formatted, flipped,
+filtered and binned by kernels (csrc/evf_resident_eval.hip, csrc/evf_resident.hip + the existing binning) and carries the keys,
+shapes, dtypes and values `H5Loader` gives on the same files, config and RNG state; `gtflow` / `frames` are gathered and flipped
+from maps and frames that live in device memory.  `data.mode: events` stays with dataloader/resident.py.
+
+Two things make these modes differ from `events`: a window's borders are TIMESTAMPS, found by `binary_search_array`, and the
+windows of a batch hold different numbers of events.  Both are settled on the host without a device value:
+
+  * Every border a file can ever be asked for is known when the file is opened -- the stamps of the configured group, or in
+    `time` mode the cursor values 0, w, w + w, ... (+ t0) up to the file's last event.  `boundary_queries` lists them, ONE
+    `evf_ts_search` launch at construction answers all of them for all files, and the table comes back to the host (the only
+    device-to-host copy).  The search runs on the files' ABSOLUTE float64 timestamps, like `H5Loader.find_ts_index`; that
+    column is needed for this one search only and is freed after it, so it is not part of `resident_bytes`.
+  * With the table on the host, the host knows every window's first event and event count before the launch: the padded
+    width of a batch is `max(count)`, and "up to 10 events is an empty window" (dataloader/h5.py:268) is `count = 0`.
+
+`ResidentEvalPlan` is the host-only half (no GPU): H5Loader's constructor, file list, sharding, flags, `reset_sequence`,
+`shuffle`, counters and `_end_pass`, plus `__getitem__`'s cursor step (dataloader/h5.py:243-311) written over the tables.
+`ResidentEvalLoader` adds the arenas and the launches.
+
+Layout in device memory: the 13-byte event arena of dataloader/resident.py (`xs`, `ys` uint16, `ts` float64 relative to the
+file's t0, `ps` uint8, one arena per column over all files), and for the mode's group either the ground-truth maps
+`[M,2,H,W]` float32 (8 H W bytes per map) or the frames `[M,H,W]` uint8 (H W bytes per frame), all files' in file order, a
+file's in the order of `_Sequence.group()`."""
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .encodings import binary_search_array, encode_event_list
+from .h5 import H5Loader, open_sequence
+from .resident import FLAG_BITS
+
+MODES = ("time", "frames", "gtflow_dt1", "gtflow_dt4")
+
+
+class ResidentEvalPlan(H5Loader):
+    """The host-only half: per slot (sequence file, first event, event count, flip flags, restarted, map index or frame indices,
+    dt_gt) of the next input window -- the decisions, counters and `np.random.random()` draws of `H5Loader.__getitem__`, in
+    its order.
+
+    meta: path -> {"events": count, "t0", "duration", "last_ts": last timestamp - t0, "names", "stamps": the mode's group};
+    read from the files when omitted.  index: path -> int64 array, `binary_search_array(events/ts, q)` for every q of
+    `boundary_queries(path)`; searched on the host when omitted (the loader searches on the device instead)."""
+
+    def __init__(self, config, num_bins, round_encoding=False, device=None, rank=0, world_size=1, meta=None, index=None):
+        mode, window = config["data"]["mode"], config["data"]["window"]
+        if mode == "events":
+            raise _lib.EvflowError("ResidentEvalLoader serves data.mode 'time', 'frames', 'gtflow_dt1' and 'gtflow_dt4'; windows by "
+                                   "event count are ResidentLoader's (or H5Loader's)")
+        if mode in MODES and (isinstance(window, bool) or not window > 0):
+            raise _lib.EvflowError(f"ResidentEvalLoader needs a data.window > 0, got {window!r}: use H5Loader")
+        self._slot_path, self._slot_step = {}, {}
+        super().__init__(config, num_bins, round_encoding, device, prefetch=0, rank=rank, world_size=world_size)
+        self.last_row = None  # (path, event index) behind `last_proc_timestamp`: last event of the last non-empty slice
+        self.meta = dict(meta) if meta is not None else self._read_meta()
+        for path in self.files:
+            if self._stamp_group() and not len(self.meta[path]["stamps"]):
+                raise _lib.EvflowError(f"{path}: no group '{self._stamp_group()}' for data.mode '{self.mode}': use H5Loader "
+                                       "on files that carry it")
+        self.queries = {path: self.boundary_queries(path) for path in self.files}
+        self.index = dict(index) if index is not None else self._search()
+        for path in self.files:
+            if len(self.index[path]) != len(self.queries[path]):
+                raise _lib.EvflowError(f"{path}: index table of {len(self.index[path])} entries for {len(self.queries[path])} "
+                                       "boundary queries")
+
+    def _open(self, batch, path):  # (H5Loader opens the slot's file here; a plan notes which one it is and rewinds)
+        self._slot_path[batch] = path
+        self._slot_step[batch] = 0  # windows handed out (or tried) since the file was opened: the row of the time table
+
+    # ------------------------------------------------------------------ what the files say
+    def _group_of(self, seq, path):
+        g = self._stamp_group()
+        if g is None:
+            return [], []
+        try:
+            names, stamps = seq.group(g)
+        except Exception:  # (h5py: KeyError, the ctypes reader: its own error -- a file without the group either way)
+            names, stamps = [], []
+        if not len(names):
+            raise _lib.EvflowError(f"{path}: no group '{g}' for data.mode '{self.mode}': use H5Loader on files that carry it")
+        return list(names), list(stamps)
+
+    def _read_meta(self):
+        out = {}
+        for path in self.files:
+            seq = open_sequence(path)
+            names, stamps = self._group_of(seq, path)
+            out[path] = {"events": len(seq.events("xs")), "t0": seq.attrs["t0"], "duration": seq.attrs["duration"],
+                         "last_ts": seq.events("ts")[-1] - seq.attrs["t0"], "names": names, "stamps": stamps}
+            seq.close()
+        return out
+
+    def boundary_queries(self, path):
+        """Every timestamp `find_ts_index` can be asked for on this file, float64: the stamps of the group, or in `time` mode
+        the pair (row + t0, row + t0 + window) of every window, row = 0 and then `+= window` like the cursor, up to and with the
+        window that makes the slot move on (h5.py:232-234,264)."""
+        m = self.meta[path]
+        if self.mode != "time":
+            return np.asarray([float(s) for s in m["stamps"]], dtype=np.float64)
+        q, row = [], 0
+        while True:
+            t = row + m["t0"]
+            q += [t, t + self.window]
+            if row + self.window >= m["last_ts"]:
+                break
+            if row + self.window == row or len(q) > (1 << 26):
+                raise _lib.EvflowError(f"{path}: a data.window of {self.window!r} s does not advance through a sequence of "
+                                       f"{m['last_ts']!r} s: use H5Loader")
+            row += self.window
+        return np.asarray(q, dtype=np.float64)
+
+    def _search(self):
+        """The index tables by the reference's own search on the host (the loader overrides this with one evf_ts_search)."""
+        out = {}
+        for path in self.files:
+            seq = open_sequence(path)
+            ts = np.asarray(seq.events("ts")[:], dtype=np.float64)
+            seq.close()
+            out[path] = np.asarray([binary_search_array(ts, q) for q in self.queries[path]], dtype=np.int64)
+        return out
+
+    # ------------------------------------------------------------------ the cursor
+    def slot_flags(self, batch):
+        return sum(bit for mech, bit in FLAG_BITS if self._flipped(mech, batch))
+
+    def _event_range(self, batch):
+        """`get_event_index` + the sub-interval arithmetic of h5.py:254-260 over the index table -> (idx0, idx1)."""
+        path = self._slot_path[batch]
+        table = self.index[path]
+        if self.mode == "time":
+            k = self._slot_step[batch]
+            return int(table[2 * k]), int(table[2 * k + 1])
+        row0, row1 = self._stamp_rows(batch, self.window)
+        idx0, idx1 = int(table[row0]), int(table[row1])
+        if self.window < 1.0:
+            idx0_change = self.batch_row[batch] - row0
+            idx1_change = self.batch_row[batch] + self.window - row0
+            delta_idx = idx1 - idx0
+            idx1 = int(idx0 + idx1_change * delta_idx)
+            idx0 = int(idx0 + idx0_change * delta_idx)
+        return idx0, idx1
+
+    def plan_sample(self, batch):
+        """dataloader/h5.py:243-311 for one slot -> (path, first event, event count, flags, restarted, indices, dt_gt);
+        indices: the map's index in its file's group (gtflow modes), (curr, next) frame indices (frames), None (time)."""
+        stamped = self.mode != "time"
+        restarted = False
+        while True:
+            path = self._slot_path[batch]
+            m = self.meta[path]
+            row = self.batch_row[batch]
+            restart = stamped and int(np.ceil(row + self.window)) >= len(m["stamps"])
+            first = count = 0
+            if not restart:
+                idx0, idx1 = self._event_range(batch)
+                n = m["events"]  # the slice [idx0:idx1] of n events
+                first = min(max(idx0, 0), n)
+                count = max(min(max(idx1, 0), n) - first, 0)
+                if count > 0:  # get_events, h5.py:212-213 -- before the restart test and the rule below
+                    self.last_row = (path, first + count - 1)
+            if self.mode == "time" and row + self.window >= m["last_ts"]:
+                restart = True
+            if count <= 10:  # very few events: an empty window (h5.py:268)
+                count = 0
+            if restart:
+                restarted = self._restarted = True
+                if not self._threaded:
+                    self.new_seq = True
+                self.reset_sequence(batch)
+                self.batch_row[batch] = 0
+                self.batch_idx[batch] = max(self.batch_idx) + 1
+                self._open(batch, self.files[self.batch_idx[batch] % len(self.files)])
+                continue
+            indices, dt_gt = None, 0.0
+            if self.mode == "frames":
+                indices = (int(np.floor(row)), int(np.ceil(row + self.window)))
+            elif stamped:
+                indices = int(np.ceil(row + self.window))
+                if indices > 0:
+                    dt_gt = m["stamps"][indices] - m["stamps"][indices - 1]
+            self.batch_row[batch] += self.window
+            self._slot_step[batch] += 1
+            return path, first, count, self.slot_flags(batch), restarted, indices, float(dt_gt)
+
+    def plan_batches(self):
+        """`H5Loader._host_batches` over the plan: ([job of slot 0, ...], (a slot restarted, wrap-around batch)) until every
+        file has been started once."""
+        while True:
+            self._restarted = False
+            jobs = [self.plan_sample(b) for b in range(self.batch_size)]
+            done = self.seq_num >= len(self.files)
+            yield jobs, (self._restarted, done)
+            if done:
+                return
+
+
+class ResidentEvalLoader(ResidentEvalPlan):
+    """`resident_bytes`: everything kept in device memory -- 13 bytes per event, 8 H W per ground-truth map or H W per frame
+    (a sequence of a few thousand 260 x 346 maps is gigabytes), the hot-pixel statistics.  The absolute timestamp column of the
+    one search at construction (8 bytes per event) is freed after it and not counted."""
+
+    def __init__(self, config, num_bins, round_encoding=False, device=None, rank=0, world_size=1):
+        super().__init__(config, num_bins, round_encoding, device, rank, world_size)  # (_read_meta, then _search on the device)
+        cols, self._cols = self._cols, None
+        dev = self.device
+        H, W = self.res
+        self._xs, self._ys, self._ts, self._ps = (torch.from_numpy(np.concatenate(c)).to(dev) for c in cols)
+        self.resident_bytes = sum(t.numel() * t.element_size() for t in (self._xs, self._ys, self._ts, self._ps))
+        self._stack = None  # the mode's maps [M,2,H,W] float32 or frames [M,H,W] uint8
+        if self._stamp_group():
+            self.stack_offsets, at = {}, 0
+            for path in self.files:
+                self.stack_offsets[path] = at
+                at += len(self.meta[path]["names"])
+            self.stack_items = at
+            shape, dtype = ((at, H, W), torch.uint8) if self.mode == "frames" else ((at, 2, H, W), torch.float32)
+            self._stack = torch.empty(shape, dtype=dtype, device=dev)
+            for path in self.files:  # (one upload per file, no second copy of everything on either side)
+                a = self._items.pop(path)
+                self._stack[self.stack_offsets[path]:self.stack_offsets[path] + len(a)].copy_(torch.from_numpy(a))
+            self.resident_bytes += self._stack.numel() * self._stack.element_size()
+        self.hot = bool(self.config["hot_filter"]["enabled"])
+        if self.hot:
+            self._hot_events = torch.zeros((self.batch_size, H, W), dtype=torch.int32, device=dev)
+            self._hot_obvs = torch.zeros(self.batch_size, dtype=torch.int32, device=dev)
+            self.resident_bytes += 4 * (self._hot_events.numel() + self._hot_obvs.numel())
+
+    # ------------------------------------------------------------------ construction
+    def _read_meta(self):
+        """Every file of the shard once: the four columns (kept in self._cols until they are uploaded; the absolute timestamps
+        in self._ts_abs until the search), the group's maps or frames (self._items), the metadata of the plan."""
+        H, W = self.res
+        g = self._stamp_group()
+        xs, ys, ts, ps, ts_abs, meta = [], [], [], [], [], {}
+        self._items = {}
+        for path in self.files:
+            seq = open_sequence(path)
+            names, stamps = self._group_of(seq, path)
+            x, y, p = (np.asarray(seq.events(k)[:]) for k in ("xs", "ys", "ps"))
+            ta = np.asarray(seq.events("ts")[:], dtype=np.float64)
+            t = ta - seq.attrs["t0"]  # get_events, h5.py:210
+            for name, c in (("xs", x), ("ys", y)):
+                if c.size and not (np.all(c == np.floor(c)) and c.min() >= 0 and c.max() <= 65535):
+                    raise _lib.EvflowError(f"{path}: events/{name} holds values that are no integers in [0, 65535]; the "
+                                           "resident arena stores uint16 coordinates: use H5Loader")
+            if p.size and not np.all((p == 0) | (p == 1)):
+                raise _lib.EvflowError(f"{path}: events/ps holds polarities outside {{0, 1}}: use H5Loader")
+            if not len(x):
+                raise _lib.EvflowError(f"{path}: no events: use H5Loader")
+            items = []
+            for name in names:
+                a = seq.read(g, name)
+                want = (H, W) if self.mode == "frames" else (2, H, W)
+                if tuple(np.shape(a)) != want:
+                    raise _lib.EvflowError(f"{path}: {g}/{name} has shape {tuple(np.shape(a))}, the loader resolution needs "
+                                           f"{want}: use H5Loader")
+                # frames: a float64 buffer cast to uint8 (h5.py:295-298); maps: augment_flowmap's float32 copy
+                items.append(np.asarray(a, dtype=np.float64).astype(np.uint8) if self.mode == "frames" else
+                             np.array(a, dtype=np.float32))
+            if items:
+                self._items[path] = np.stack(items)
+            meta[path] = {"events": len(x), "t0": seq.attrs["t0"], "duration": seq.attrs["duration"],
+                          "last_ts": seq.events("ts")[-1] - seq.attrs["t0"], "names": names, "stamps": stamps}
+            seq.close()
+            xs.append(x.astype(np.uint16))
+            ys.append(y.astype(np.uint16))
+            ts.append(t)
+            ps.append(p.astype(np.uint8))
+            ts_abs.append(ta)
+        self._cols, self._ts_abs = (xs, ys, ts, ps), ts_abs
+        self.offsets, at = {}, 0
+        for path in self.files:
+            self.offsets[path] = at
+            at += meta[path]["events"]
+        self.total_events = at
+        return meta
+
+    def _search(self):
+        """Every boundary query of every file in one evf_ts_search on the absolute timestamps -> the plan's index tables.
+        Everything before this was host work (the refusals); this is the first device work and the only copy back."""
+        _lib.load()
+        if not torch.cuda.is_available():
+            raise _lib.EvflowError("ResidentEvalLoader: the sequences live and are cut on the MI355X only (no CPU fallback)")
+        dev = self.device
+        ts_abs, self._ts_abs = self._ts_abs, None
+        begin = np.concatenate([np.full(len(self.queries[p]), self.offsets[p], dtype=np.int64) for p in self.files])
+        length = np.concatenate([np.full(len(self.queries[p]), self.meta[p]["events"], dtype=np.int64) for p in self.files])
+        query = np.concatenate([self.queries[p] for p in self.files])
+        col = torch.from_numpy(np.concatenate(ts_abs)).to(dev)
+        b, n, q = (torch.from_numpy(a).to(dev) for a in (begin, length, query))
+        out = torch.empty(len(query), dtype=torch.int64, device=dev)
+        _lib.call("evf_ts_search", _lib.ptr(col), self.total_events, _lib.ptr(b), _lib.ptr(n), _lib.ptr(q), len(query), _lib.ptr(out))
+        found = out.cpu().numpy()
+        del col
+        if (found < 0).any():
+            raise _lib.EvflowError("evf_ts_search: a segment outside the timestamp column")
+        tables, at = {}, 0
+        for p in self.files:
+            tables[p] = found[at:at + len(self.queries[p])]
+            at += len(self.queries[p])
+        return tables
+
+    # ------------------------------------------------------------------ launches
+    def _job_table(self, jobs):
+        """The host table of one planned batch as int64 words: `first` int64 [B] | `dt_gt` float64 [B] | as int32 `count` [B],
+        `flags` [B], `reset` [B], two index columns [B] each (map index, or curr and next frame; into the resident stack)."""
+        B = self.batch_size
+        tab = np.zeros(2 * B + (5 * B + 1) // 2, dtype=np.int64)
+        dt_gt = tab[B:2 * B].view(np.float64)
+        aux = tab[2 * B:].view(np.int32)
+        for b, (path, first, count, flags, restarted, indices, dt) in enumerate(jobs):
+            tab[b] = self.offsets[path] + first
+            dt_gt[b] = dt
+            aux[b], aux[B + b], aux[2 * B + b] = count, flags, 1 if restarted else 0
+            if indices is not None:
+                i0, i1 = indices if isinstance(indices, tuple) else (indices, indices)
+                aux[3 * B + b], aux[4 * B + b] = self.stack_offsets[path] + i0, self.stack_offsets[path] + i1
+        return tab
+
+    def _produce(self, jobs):
+        """One planned batch -> the reference's batch dict (dataloader/base.py:248-265): one copy of the job table, then the
+        cut, the hot-pixel filter, the binning, the masks and the gather."""
+        B = self.batch_size
+        H, W = self.res
+        dev = self.device
+        npad = max(j[2] for j in jobs)  # known on the host: no device value decides a shape
+        N = max(npad, 1)
+        t = torch.from_numpy(self._job_table(jobs)).pin_memory().to(dev, non_blocking=True)
+        at = t.data_ptr()
+        aux = at + 16 * B
+        ev = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
+        dt = torch.empty(B, dtype=torch.float64, device=dev)
+        _lib.call("evf_seq_cut_ragged", _lib.ptr(self._xs), _lib.ptr(self._ys), _lib.ptr(self._ts), _lib.ptr(self._ps),
+                  self.total_events, at, aux, aux + 4 * B, B, N, H, W, _lib.ptr(ev), _lib.ptr(dt))
+        mask = None
+        if self.hot:  # (an empty window is an observation too, like create_hot_mask's)
+            hf = self.config["hot_filter"]
+            mask = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+            _lib.call("evf_hot_pixels", _lib.ptr(ev), aux + 8 * B, _lib.ptr(self._hot_events), _lib.ptr(self._hot_obvs), _lib.ptr(mask),
+                      None, B, 1, N, H, W, int(hf["max_px"]), int(hf["min_obvs"]), float(hf["max_rate"]))
+        out = encode_event_list(ev, self.num_bins, self.res, round_ts=self.round_encoding)
+        if npad == 0:  # only padding rows: empty lists, like custom_collate
+            out["event_list"] = out["event_list"][:, :0]
+            out["event_list_pol_mask"] = out["event_list_pol_mask"][:, :0]
+        if mask is not None:
+            for key, C in (("event_voxel", self.num_bins), ("event_cnt", 2), ("event_mask", 1)):
+                _lib.call("evf_apply_pixel_mask", _lib.ptr(out[key]), _lib.ptr(mask), B, C, H, W)
+        out["dt_gt"] = t[B:2 * B].view(torch.float64)
+        out["dt_input"] = dt
+        if self.mode == "frames":
+            out["frames"] = torch.empty((B, 2, H, W), dtype=torch.uint8, device=dev)
+            _lib.call("evf_gather_frames", _lib.ptr(self._stack), self.stack_items, aux + 12 * B, aux + 16 * B, aux + 4 * B, B, H, W,
+                      _lib.ptr(out["frames"]))
+        elif self._stack is not None:
+            out["gtflow"] = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev)
+            _lib.call("evf_gather_flowmaps", _lib.ptr(self._stack), self.stack_items, aux + 12 * B, aux + 4 * B, B, H, W,
+                      _lib.ptr(out["gtflow"]))
+        return out
+
+    def __iter__(self):
+        """The batches of one pass over the files, like `H5Loader.__iter__` with its flags: no reader thread, no device
+        synchronisation."""
+        try:
+            for jobs, (restarted, done) in self.plan_batches():
+                batch = self._produce(jobs)
+                self.new_seq, self.pass_done = restarted, done
+                self.samples += self.batch_size
+                yield batch
+        finally:
+            self._end_pass()
+
+    # ------------------------------------------------------------------ one value on demand
+    @property
+    def last_proc_timestamp(self):
+        """Timestamp (relative to its file's t0) of the last event of the last non-empty slice, before the rule that empties
+        windows of up to 10 events (`get_events`): fetched from the arena when asked for."""
+        if self.last_row is not None:
+            path, row = self.last_row
+            self._last_ts = float(self._ts[self.offsets[path] + row])
+            self.last_row = None
+        return self._last_ts
+
+    @last_proc_timestamp.setter
+    def last_proc_timestamp(self, value):
+        self.last_row, self._last_ts = None, value

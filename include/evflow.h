@@ -721,6 +721,35 @@ int evf_hot_pixels(const float* ev, const int* reset, int* events, int* obvs, fl
  * misaligned segment, a negative size or one that is no multiple of 4. */
 int evf_zero_segments_if(const int* flag, void* const* dst, const int64_t* bytes, int nseg, void* stream);
 
+/* ------------------------------------------------------------------ device-resident evaluation
+ * (dataloader/resident_eval.py, csrc/evf_resident_eval.hip): data.mode time / frames / gtflow_dt1 / gtflow_dt4 on the arena
+ * above.  Every entry: EVF_EINVAL for a null pointer, a non-positive size or a grid beyond the launch limits.
+ *
+ * evf_ts_search: out[q] (int64, relative to the segment) = binary_search_array(ts[seg_begin[q] : seg_begin[q] + seg_len[q]],
+ * query[q]) of dataloader/encodings.py, step for step: mid = lo + (hi - lo) / 2, the first element met that equals the query
+ * (among duplicates not the leftmost), else the final lo (0 .. seg_len).  ts: `total` float64 timestamps, sorted inside every
+ * segment, ABSOLUTE (the files' events/ts, which H5Loader.find_ts_index searches); seg_begin / seg_len int64 [Q], query
+ * float64 [Q], all in device memory.  One thread per query.  A segment that leaves the column answers -1. */
+int evf_ts_search(const double* ts, int64_t total, const int64_t* seg_begin, const int64_t* seg_len, const double* query,
+                  int64_t Q, int64_t* out, void* stream);
+/* evf_seq_cut_ragged: evf_seq_cut with an event count per job.  Job j takes count[j] (int32) events from arena index first[j]
+ * (int64) on and writes them as rows 0 .. count[j] - 1 of ev [J][Npad][4], formatted and flipped exactly like evf_seq_cut
+ * (normalised by the job's own first and last event); rows count[j] .. Npad - 1 are all zero.  dt_input [J] float64 =
+ * ts[last] - ts[first], 0 for an empty job.  A job with first < 0, count < 0, count > Npad or first + count > total is all
+ * padding with dt_input 0 and reads nothing.  J <= 65535. */
+int evf_seq_cut_ragged(const uint16_t* xs, const uint16_t* ys, const double* ts, const uint8_t* ps, int64_t total,
+                       const int64_t* first, const int* count, const int* flags, int J, int Npad, int H, int W, float* ev,
+                       double* dt_input, void* stream);
+/* evf_gather_flowmaps: out [B][2][H][W] = augment_flowmap(maps[idx[b]]) (dataloader/base.py:90-98) of resident ground-truth
+ * maps [M][2][H][W] float32: flags[b] bit 0 reverses x and negates component 0, bit 1 reverses y and negates component 1.
+ * evf_gather_frames: out [B][2][H][W] uint8 = augment_frames of frames[curr[b]] and frames[next[b]] (frames [M][H][W] uint8).
+ * idx / curr / next / flags: int32 [B] in device memory; an index outside 0 .. M - 1 gives zeros.  16-byte accesses in both
+ * row directions when W is a multiple of 4 (maps) / 16 (frames) and both tensors are 16-byte aligned, else element-wise. */
+int evf_gather_flowmaps(const float* maps, int M, const int* idx, const int* flags, int B, int H, int W, float* out,
+                        void* stream);
+int evf_gather_frames(const uint8_t* frames, int M, const int* curr, const int* next, const int* flags, int B, int H, int W,
+                      uint8_t* out, void* stream);
+
 /* Window masks: out [B,1,H,W] = min(sum_p masks[B,P,H,W], 1) (loss/flow.py:149-150); masked mean of the
  * per-pass flow maps [B,P,2,H,W] -> [B,2,H,W], sum_p maps*mask / (sum_p mask + 1e-9) (loss/flow.py:443-452). */
 int evf_mask_union(const float* masks, int B, int P, int H, int W, float* out, void* stream);

@@ -9,6 +9,7 @@ Cases, alternating inside one process after a warm-up, each timed for at least `
   resident_window   ResidentLoader.next_window(10)
 with and without the hot-pixel filter.  Reported: milliseconds per 80 samples, host clock around a final device
 synchronise.  Sequence files: `.npz`, generated from --seed into a temporary directory (so no HDF5 reads are in the numbers).
+The evaluation modes (time / gtflow windows, ResidentEvalLoader) are measured by tools/eval_loader_rate.py.
 
   python tools/loader_rate.py [--seconds 2] [--out profiles/loader_rate.json]
 """
