@@ -4,6 +4,7 @@ exactly as the reference loop does (association per input window, metric once `w
 No MLflow / visualiser; results are printed as JSON.
 
   python eval_flow.py --config configs/eval_flow.yml --train-config configs/train_SNN.yml --synthetic [--weights model.pth]
+  python eval_flow.py ... --resident --graphed [--per-sequence]   # data.mode events: a graph launch per evaluated window
 """
 
 import argparse
@@ -12,14 +13,17 @@ import json
 import numpy as np
 import torch
 
+from event_flow_amd import _lib
 from event_flow_amd.configs.parser import YAMLParser
+from event_flow_amd.evaluate import PerSequence, ResidentEvalStep, graphed_refusal, slot_files
 from event_flow_amd.loss import flow as metrics_mod
 from event_flow_amd.models.model import MODELS
 from event_flow_amd.utils.iwe import compute_pol_iwe
 from event_flow_amd.utils.utils import load_model
 
 
-def test(args, config_parser):
+def test(args, config_parser, graphed_replay=True):
+    """`graphed_replay=False`: with --graphed, the same launches without the graph replay (A/B, tests)."""
     # the reference overlays the eval YAML on the training run's stored parameters (merge_configs); here the
     # training YAML plays the role of the stored run
     train_cfg = YAMLParser(args.train_config).config
@@ -34,6 +38,17 @@ def test(args, config_parser):
     config["data"].setdefault("window_eval", config["data"]["window"])
     config["loss"] = config.get("loss", {"overwrite_intermediate": False})
     device = config_parser.device
+    graphed, per_sequence = getattr(args, "graphed", False), getattr(args, "per_sequence", False)
+    model = None
+    if graphed:  # refused on the host, before any device work (which path serves a network is a property of its cells)
+        why = graphed_refusal(args, config)
+        if not why:
+            model = MODELS[config["model"]["name"]](config["model"].copy())
+            why = graphed_refusal(args, config, model)
+        if why:
+            raise _lib.EvflowError(why)
+    if per_sequence and args.synthetic:
+        raise _lib.EvflowError("--per-sequence reports per sequence FILE; the synthetic loader reads none: drop --synthetic")
     if torch.device(device).type == "cuda":
         torch.cuda.set_device(device)  # the evf_* launches go to the current device's stream (loader.gpu may not be 0)
 
@@ -51,7 +66,7 @@ def test(args, config_parser):
         else:
             assert np.isclose(config["data"]["window"] % 1.0, 0.0), "Frames mode not compatible with > 1 fractional windows"
 
-    model = MODELS[config["model"]["name"]](config["model"].copy()).to(device)
+    model = (model if model is not None else MODELS[config["model"]["name"]](config["model"].copy())).to(device)
     if args.weights:  # a state_dict file, a reference checkpoint (pickled model) or its MLflow run id under ./mlruns
         model = load_model(args.weights, model, device)
     model.eval()
@@ -73,13 +88,17 @@ def test(args, config_parser):
     else:
         from event_flow_amd.dataloader.h5 import H5Loader
 
-        data = H5Loader(config, config["model"]["num_bins"], device=device)
+        # (--per-sequence asks the loader which file a slot reads while its batch is out: no reader thread running ahead)
+        data = H5Loader(config, config["model"]["num_bins"], device=device, **({"prefetch": 0} if per_sequence else {}))
 
     vis = None
     if args.store:  # stored PNGs in the reference's folder layout (utils/visualization.py:120-226); batch size 1
         from event_flow_amd.utils.visualization import Visualization
 
         vis = Visualization(config, eval_id=0, path_results=args.store.rstrip("/") + "/")
+    if graphed:
+        return _test_graphed(config, model, criteria, names, data, per_sequence, graphed_replay)
+    per_seq = PerSequence() if per_sequence else None
     results = {m: {"metric": 0.0, "it": 0, **({"percent": 0.0} if m == "AEE" else {})} for m in names}
     iwe_sharpness = []
     idx_AEE = 0  # sub-windows since the last AEE evaluation (eval_flow.py:117,171-176)
@@ -123,12 +142,40 @@ def test(args, config_parser):
                         results[name]["percent"] += float(val[1].mean())
                     else:
                         results[name]["metric"] += float(val.mean())
+                    if per_seq is not None:  # a slot's value goes to the file that slot reads now (eval_flow.py:183-199)
+                        files = slot_files(data)
+                        if name == "AEE":
+                            per_seq.add("AEE", files, val[0].reshape(-1).tolist())
+                            per_seq.add("AEE_percent_outliers", files, val[1].reshape(-1).tolist())
+                        else:
+                            per_seq.add(name, files, val.reshape(-1).tolist())
                     criteria[i].reset()
     out = {"model": config["model"]["name"], "iwe_variance": float(torch.stack(iwe_sharpness).mean())}
     for name, r in results.items():
         out[name] = r["metric"] / max(r["it"], 1)
         if name == "AEE":
             out["AEE_percent_outliers"] = r["percent"] / max(r["it"], 1)
+    if per_seq is not None:
+        out["per_sequence"] = per_seq.summary()
+    print(json.dumps(out))
+    return out
+
+
+def _test_graphed(config, model, criteria, names, data, per_sequence, replay):
+    """The loop above for `data.mode: events` on the resident loader, an evaluated window (P = ceil(window_eval / window)
+    batches) per step: one table copy and one graph launch each, the results read once at the end (evaluate.py)."""
+    P = -(-int(config["data"]["window_eval"]) // int(config["data"]["window"]))
+    steps = list(data.plan_eval_steps(P))  # host-only: the number of evaluated windows sizes the result log
+    stepper = ResidentEvalStep(model, criteria, names, data, P, len(steps) - 1, config["metrics"]["flow_scaling"],
+                               overwrite_intermediate=config["loss"].get("overwrite_intermediate", False), replay=replay,
+                               per_sequence=per_sequence)
+    model.reset_states()
+    for group, pass_reset, tail in steps:
+        if tail:
+            stepper.step_tail(group, pass_reset)
+        else:
+            stepper.step(group, pass_reset)
+    out = {"model": config["model"]["name"], **stepper.results(), "graphed": dict(stepper.stats)}
     print(json.dumps(out))
     return out
 
@@ -144,6 +191,12 @@ if __name__ == "__main__":
                         help="keep the sequence files in device memory and cut the input windows there (every data.mode: "
                              "ResidentLoader for events, ResidentEvalLoader with resident ground-truth maps / frames for time, "
                              "frames, gtflow_dt1 and gtflow_dt4)")
+    parser.add_argument("--graphed", action="store_true",
+                        help="with --resident and data.mode events: every evaluated window (window_eval events) is one job-table "
+                             "copy plus one hipGraph launch, results logged on the device and read once at the end (fused "
+                             "LIF / PLIF / XLIF / ALIF FireNets; FWL / RSAT)")
+    parser.add_argument("--per-sequence", action="store_true", dest="per_sequence",
+                        help="also report every metric per sequence file (\"per_sequence\": {file: {metric: mean, \"it\": n}})")
     parser.add_argument("--store", default="", help="directory that receives results/eval_0/<sequence>/{events,flow,iwe,...}/*.png")
     args = parser.parse_args()
     test(args, YAMLParser(args.config))

@@ -56,6 +56,8 @@ SIGNATURES = {
     "evf_hot_pixels": [P, P, P, P, P, P, I, I, I, I, I, I, I, F, P],
     # conditional zero-fill of up to 32 segments: device flag (or NULL), host arrays dst / bytes (int64), nseg
     "evf_zero_segments_if": [P, P, P, I, P],
+    # result log of a replayed evaluation step: device row word, nrows, log, row_floats, host arrays src / offset / n, nseg
+    "evf_store_segments_at": [P, L, P, L, P, P, P, I, P],
     # device-resident evaluation (dataloader/resident_eval.py): ts, total, seg_begin, seg_len, query, Q, out
     "evf_ts_search": [P, L, P, P, P, L, P, P],
     # arena columns, total, first, count, flags, J, Npad, H, W, ev, dt_input

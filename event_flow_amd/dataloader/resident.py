@@ -121,6 +121,34 @@ class ResidentPlan(H5Loader):
             yield discarded, group, reset, epoch
             wraps = epoch + (1 if group[-1][2] else 0)
 
+    def plan_eval_steps(self, P):
+        """ONE pass over the files as eval_flow.py's loop meets it: the batches of `plan_batches()` up to, not including, the
+        wrap-around (`done`) batch -- the loop breaks on that one before forwarding it -- in groups of P consecutive batches:
+        (group, pass_reset, tail) per group, `group` P batches (jobs, restarted, done) like `plan_window`'s, `pass_reset[p]`
+        whether batch p restarted a slot (the loop's `model.reset_states()` in front of that pass), `tail` False; at the end
+        once (rest, its pass_reset, True) with the fewer than P batches left over (possibly none).  The loop does not reset
+        its criteria at a new sequence and every batch adds `window` events, so a criterion fires after every P =
+        ceil(window_eval / window) batches whatever restarts: the groups are the metric windows.  Independent of
+        `plan_window` / `plan_steps` (it does not touch their stream); the loader's flags, sample counter and end-of-pass
+        bookkeeping move as in `__iter__`."""
+        P = int(P)
+        if P < 1:
+            raise _lib.EvflowError(f"plan_eval_steps: groups of {P} batches")
+        group = []
+        try:
+            for jobs, (restarted, done) in self.plan_batches():
+                self.new_seq, self.pass_done = restarted, done
+                self.samples += self.batch_size
+                if done:
+                    break
+                group.append((jobs, restarted, done))
+                if len(group) == P:
+                    yield group, [r for _j, r, _d in group], False
+                    group = []
+            yield group, [r for _j, r, _d in group], True
+        finally:
+            self._end_pass()
+
 
 class ResidentLoader(ResidentPlan):
     def __init__(self, config, num_bins, round_encoding=False, device=None, rank=0, world_size=1):

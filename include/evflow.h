@@ -720,6 +720,17 @@ int evf_hot_pixels(const float* ev, const int* reset, int* events, int* obvs, fl
  * aligned, every bytes a multiple of 4 (0 allowed).  EVF_EINVAL: dst or bytes NULL, nseg outside 1..32, a NULL or
  * misaligned segment, a negative size or one that is no multiple of 4. */
 int evf_zero_segments_if(const int* flag, void* const* dst, const int64_t* bytes, int nseg, void* stream);
+/* evf_store_segments_at (csrc/evf_eval_log.hip): the results of a replayed evaluation step appended to a device log
+ * (evaluate.ResidentEvalStep), log[row[0] * row_floats + offset[k] + i] = src[k][i] for i < n[k], k < nseg, in one launch.
+ * row: ONE int64 word in DEVICE memory, read by the kernel (the step number the host put into the step's job table); a word
+ * outside 0 .. nrows - 1 is a defined no-op, nothing is written.  log: nrows rows of row_floats floats.  src / offset / n:
+ * HOST arrays of nseg <= 32 entries, passed by value in the launch's arguments (the evf_add_segments convention), so the call
+ * allocates nothing, copies nothing and can be captured; every source is float32 device memory, 4-byte aligned, n[k] == 0
+ * allowed.  Plain loads and stores, no atomics: segments of one call must not overlap in the row.  EVF_EINVAL, before any
+ * launch: row, log, src, offset or n NULL, nseg outside 1..32, a NULL or misaligned source, a negative n[k] or offset[k],
+ * offset[k] + n[k] > row_floats. */
+int evf_store_segments_at(const int64_t* row, int64_t nrows, float* log, int64_t row_floats, const void* const* src,
+                          const int* offset, const int* n, int nseg, void* stream);
 
 /* ------------------------------------------------------------------ device-resident evaluation
  * (dataloader/resident_eval.py, csrc/evf_resident_eval.hip): data.mode time / frames / gtflow_dt1 / gtflow_dt4 on the arena
