@@ -7,9 +7,8 @@
 //   evf_zero_segments_if  the recurrent state's reset as a node of a replayed step: zero-fill under a device flag.
 //
 // All are plain streaming kernels: a c3 window is 80 jobs x 1000 events (1 MB of rows) and 80 masks of 128 x 128 pixels.
-// Built with -ffp-contract=off; the float division below is the correctly rounded one, so the normalised timestamps carry
-// numpy's bits.
-#include "evf_common.h"
+// The row of an event is evf_seq_row (evf_seq_row.h), shared with evf_seq_cut_ragged.
+#include "evf_seq_row.h"
 
 // --------------------------------------------------------------------------
 // evf_seq_cut
@@ -24,24 +23,8 @@ __global__ void k_seq_cut(const uint16_t* __restrict__ xs, const uint16_t* __res
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   const long f = (long)first[j];
-  float4* row = ev + (long)j * N + n;
   const int b = j / P, p = j - b * P;
-  if (f < 0 || f > total - N) {
-    *row = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (n == 0) dt_input[(long)p * B + b] = 0.0;
-    return;
-  }
-  const int fl = flags[j];
-  const double d0 = ts[f], d1 = ts[f + N - 1];
-  const float t0 = (float)d0, t1 = (float)d1;  // base.py:64: float32 first, then the normalisation in float32
-  const float t = ((float)ts[f + n] - t0) / (t1 - t0);
-  float x = (float)xs[f + n], y = (float)ys[f + n];
-  float pol = (float)ps[f + n] * 2.0f - 1.0f;
-  if (fl & 1) x = (float)(W - 1) - x;
-  if (fl & 2) y = (float)(H - 1) - y;
-  if (fl & 4) pol = -pol;
-  *row = make_float4(t, y, x, pol);
-  if (n == 0) dt_input[(long)p * B + b] = d1 - d0;
+  evf_seq_row(xs, ys, ts, ps, f >= 0 && f <= total - N, f, N, n, flags + j, H, W, ev + (long)j * N + n, dt_input + (long)p * B + b);
 }
 
 extern "C" int evf_seq_cut(const uint16_t* xs, const uint16_t* ys, const double* ts, const uint8_t* ps, int64_t total,

@@ -7,9 +7,9 @@
 //   evf_gather_flowmaps  augment_flowmap of resident ground-truth maps picked by index.
 //   evf_gather_frames    augment_frames of two resident APS frames per slot.
 //
-// All are streaming kernels, one thread per query / event / 16 bytes of output.  Built with -ffp-contract=off; the float
-// division of the cut is the correctly rounded one (numpy's bits).
-#include "evf_common.h"
+// All are streaming kernels, one thread per query / event / 16 bytes of output.  The row of an event is evf_seq_row
+// (evf_seq_row.h), shared with evf_seq_cut.
+#include "evf_seq_row.h"
 
 #define RE_THREADS 256
 
@@ -59,8 +59,8 @@ extern "C" int evf_ts_search(const double* ts, int64_t total, const int64_t* seg
 // evf_seq_cut_ragged
 // --------------------------------------------------------------------------
 // Job j reads events first[j] .. first[j] + count[j] - 1 of the arena into rows 0 .. count[j] - 1 of its Npad rows; the rows
-// behind are zero.  Formatting and flips are k_seq_cut's (csrc/evf_resident.hip).  A job with a negative first or count, a
-// count above Npad or a range that leaves the arena is all padding with dt = 0: nothing is read out of bounds.
+// behind are zero.  A job with a negative first or count, a count above Npad or a range that leaves the arena is all padding
+// with dt = 0: nothing is read out of bounds.
 __global__ void __launch_bounds__(RE_THREADS)
 k_seq_cut_ragged(const uint16_t* __restrict__ xs, const uint16_t* __restrict__ ys, const double* __restrict__ ts,
                  const uint8_t* __restrict__ ps, long total, const long long* __restrict__ first, const int* __restrict__ count,
@@ -70,24 +70,9 @@ k_seq_cut_ragged(const uint16_t* __restrict__ xs, const uint16_t* __restrict__ y
   if (n >= Npad) return;
   const long f = (long)first[j];
   const long c = (long)count[j];
-  float4* row = ev + (long)j * Npad + n;
   const bool ok = c > 0 && c <= (long)Npad && f >= 0 && f <= total - c;
-  if (!ok || n >= c) {
-    *row = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (n == 0) dt_input[j] = 0.0;  // (n == 0 < c in a valid job with events: only an empty or refused job comes here)
-    return;
-  }
-  const int fl = flags[j];
-  const double d0 = ts[f], d1 = ts[f + c - 1];
-  const float t0 = (float)d0, t1 = (float)d1;  // base.py:64: float32 first, then the normalisation in float32
-  const float t = ((float)ts[f + n] - t0) / (t1 - t0);
-  float x = (float)xs[f + n], y = (float)ys[f + n];
-  float pol = (float)ps[f + n] * 2.0f - 1.0f;
-  if (fl & 1) x = (float)(W - 1) - x;
-  if (fl & 2) y = (float)(H - 1) - y;
-  if (fl & 4) pol = -pol;
-  *row = make_float4(t, y, x, pol);
-  if (n == 0) dt_input[j] = d1 - d0;
+  // (n == 0 < c in a valid job with events: only an empty or refused job writes dt = 0)
+  evf_seq_row(xs, ys, ts, ps, ok && n < c, f, c, n, flags + j, H, W, ev + (long)j * Npad + n, dt_input + j);
 }
 
 extern "C" int evf_seq_cut_ragged(const uint16_t* xs, const uint16_t* ys, const double* ts, const uint8_t* ps, int64_t total,

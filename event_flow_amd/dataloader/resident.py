@@ -1,26 +1,28 @@
 """Device-resident event sequences: every sequence file of the loader's shard is uploaded ONCE, and every batch -- or every
 whole BPTT window -- is then cut, formatted, flipped, filtered and binned by kernels (csrc/evf_resident.hip + the existing
-binning), with the keys, shapes, dtypes and values `H5Loader` gives on the same files, flags and RNG state.
+binning), with the keys, shapes, dtypes and values `H5Loader` gives on the same files, flags and RNG state.  The cursor, the column reader and the arena are shared with the
+evaluation loader: dataloader/resident_base.py.
 
 Only `data.mode: events` (the training mode): there the next window of a slot is index arithmetic on the sequence LENGTHS,
-so the host decides everything without a device value.  That decision is `ResidentPlan` -- H5Loader's own constructor, file
-list, sharding, augmentation flags, `reset_sequence`, `shuffle`, counters and `_end_pass`, plus the cursor step of
-dataloader/h5.py:244-279,310 written over lengths.  It needs no GPU.  `ResidentLoader` adds the arena and the launches.
+so the host decides everything without a device value.  That decision is `ResidentPlan` -- `ResidentCursor` plus the cursor
+step of dataloader/h5.py:244-279,310 written over lengths.  It needs no GPU.  `ResidentLoader` adds the arena and the launches,
+`ResidentWindow` the static buffers of a window that is cut again and again (the graph-replayed steppers).
 
 Layout in device memory: one arena per column over all files, `xs`, `ys` uint16, `ts` float64 RELATIVE to its file's t0
 (subtracted on the host in float64 exactly like `get_events`), `ps` uint8 -- 13 bytes per event -- and int64 offsets."""
+
+import ctypes
 
 import numpy as np
 import torch
 
 from .. import _lib
 from .encodings import encode_event_list, encode_window
-from .h5 import H5Loader, open_sequence
+from .h5 import open_sequence
+from .resident_base import FLAG_BITS, ResidentArena, ResidentCursor, read_columns  # noqa: F401  (FLAG_BITS: imported from here)
 
-FLAG_BITS = (("Horizontal", 1), ("Vertical", 2), ("Polarity", 4))
 
-
-class ResidentPlan(H5Loader):
+class ResidentPlan(ResidentCursor):
     """The host-only half: which (sequence file, first event, flip flags) every slot reads next, and whether the slot
     restarted on the way -- the same decisions, counters and `np.random.random()` draws, in the same order, as
     `H5Loader.__getitem__` in `events` mode.  `lengths`: events per file (path -> int); read from the files when omitted."""
@@ -41,9 +43,6 @@ class ResidentPlan(H5Loader):
             raise _lib.EvflowError(f"no sequence file holds one window of {self.window} events")
         self._stream = None
 
-    def _open(self, batch, path):  # (H5Loader opens the slot's file here; a plan only notes which one it is)
-        self._slot_path[batch] = path
-
     def _read_lengths(self):
         out = {}
         for path in self.files:
@@ -52,41 +51,21 @@ class ResidentPlan(H5Loader):
             seq.close()
         return out
 
-    def slot_flags(self, batch):
-        return sum(bit for mech, bit in FLAG_BITS if self._flipped(mech, batch))
-
     def plan_sample(self, batch):
         """dataloader/h5.py:244-279,310 for one slot -> (path, first event, flags, restarted)."""
         restarted = False
         while self.lengths[self._slot_path[batch]] - self.batch_row[batch] < self.window:  # fewer events left than a window
-            restarted = self._restarted = True
-            if not self._threaded:
-                self.new_seq = True
-            self.reset_sequence(batch)
-            self.batch_row[batch] = 0
-            self.batch_idx[batch] = max(self.batch_idx) + 1
-            self._open(batch, self.files[self.batch_idx[batch] % len(self.files)])
+            restarted = True
+            self._restart(batch)
         first = self.batch_row[batch]
         self.batch_row[batch] += self.window
         return self._slot_path[batch], first, self.slot_flags(batch), restarted
-
-    def plan_batches(self):
-        """`H5Loader._host_batches` over the plan: ([job of slot 0, ...], (a slot restarted, wrap-around batch)) until
-        every file has been started once."""
-        while True:
-            self._restarted = False
-            jobs = [self.plan_sample(b) for b in range(self.batch_size)]
-            done = self.seq_num >= len(self.files)
-            yield jobs, (self._restarted, done)
-            if done:
-                return
 
     def _endless(self):
         """The batches of pass after pass over the files, as the training driver meets them: (jobs, restarted, done)."""
         while True:
             for jobs, (restarted, done) in self.plan_batches():
-                self.new_seq, self.pass_done = restarted, done  # (H5Loader._deliver's bookkeeping)
-                self.samples += self.batch_size
+                self._delivered(restarted, done)
                 yield jobs, restarted, done
             self._end_pass()
 
@@ -137,8 +116,7 @@ class ResidentPlan(H5Loader):
         group = []
         try:
             for jobs, (restarted, done) in self.plan_batches():
-                self.new_seq, self.pass_done = restarted, done
-                self.samples += self.batch_size
+                self._delivered(restarted, done)
                 if done:
                     break
                 group.append((jobs, restarted, done))
@@ -150,49 +128,25 @@ class ResidentPlan(H5Loader):
             self._end_pass()
 
 
-class ResidentLoader(ResidentPlan):
+class ResidentLoader(ResidentArena, ResidentPlan):
     def __init__(self, config, num_bins, round_encoding=False, device=None, rank=0, world_size=1):
         super().__init__(config, num_bins, round_encoding, device, rank, world_size)  # (reads the columns: _read_lengths)
         cols, self._cols = self._cols, None
         _lib.load()  # the refusals above are host work; from here on the device
         if not torch.cuda.is_available():
             raise _lib.EvflowError("ResidentLoader: the sequences live and are cut on the MI355X only (no CPU fallback)")
-        dev = self.device
-        self.offsets, at = {}, 0
-        for path in self.files:
-            self.offsets[path] = at
-            at += self.lengths[path]
-        self.total_events = at
-        self._xs, self._ys, self._ts, self._ps = (torch.from_numpy(np.concatenate(c)).to(dev) for c in cols)
-        self.resident_bytes = sum(t.numel() * t.element_size() for t in (self._xs, self._ys, self._ts, self._ps))
-        H, W = self.res
-        self.hot = bool(self.config["hot_filter"]["enabled"])
-        if self.hot:
-            self._hot_events = torch.zeros((self.batch_size, H, W), dtype=torch.int32, device=dev)
-            self._hot_obvs = torch.zeros(self.batch_size, dtype=torch.int32, device=dev)
-        self._last_row = None
-        self._last_ts = 0
+        self._place(self.lengths)
+        self._upload(cols)
 
     def _read_lengths(self):
         """Every file's four columns, once (kept in self._cols until they are uploaded) -> their lengths."""
-        xs, ys, ts, ps, lengths = [], [], [], [], {}
+        self._cols, lengths = ([], [], [], []), {}
         for path in self.files:
             seq = open_sequence(path)
-            x, y, p = (np.asarray(seq.events(k)[:]) for k in ("xs", "ys", "ps"))
-            t = np.asarray(seq.events("ts")[:], dtype=np.float64) - seq.attrs["t0"]  # get_events, h5.py:210
+            for col, c in zip(self._cols, read_columns(seq, path)):  # (the absolute timestamps are not kept)
+                col.append(c)
             seq.close()
-            for name, c in (("xs", x), ("ys", y)):
-                if c.size and not (np.all(c == np.floor(c)) and c.min() >= 0 and c.max() <= 65535):
-                    raise _lib.EvflowError(f"{path}: events/{name} holds values that are no integers in [0, 65535]; the "
-                                           "resident arena stores uint16 coordinates: use H5Loader")
-            if p.size and not np.all((p == 0) | (p == 1)):
-                raise _lib.EvflowError(f"{path}: events/ps holds polarities outside {{0, 1}}: use H5Loader")
-            lengths[path] = len(x)
-            xs.append(x.astype(np.uint16))
-            ys.append(y.astype(np.uint16))
-            ts.append(t)
-            ps.append(p.astype(np.uint8))
-        self._cols = (xs, ys, ts, ps)
+            lengths[path] = len(self._cols[0][-1])
         return lengths
 
     # ------------------------------------------------------------------ launches
@@ -200,7 +154,7 @@ class ResidentLoader(ResidentPlan):
         """The host table of P planned batches, job j = b * P + p: `first` int64 [B*P], then as int32 `flags` [B*P] | slot
         `reset` [B*P] | the window's `reset` (did the first batch restart a slot: train_flow.py's loop reset the model in front
         of it) -- one int64 array of 2*B*P + 1 words."""
-        B, P, N = self.batch_size, len(batches), self.window
+        B, P = self.batch_size, len(batches)
         tab = np.zeros(2 * B * P + 1, dtype=np.int64)
         aux = tab[B * P:].view(np.int32)
         for p, (jobs, _restarted, _done) in enumerate(batches):
@@ -209,77 +163,76 @@ class ResidentLoader(ResidentPlan):
                 aux[b * P + p] = flags
                 aux[B * P + b * P + p] = 1 if restarted else 0
         aux[2 * B * P] = 1 if batches[0][1] else 0
-        self._last_row = int(tab[B * P - 1]) + N - 1  # last event of the last slot's last pass
+        self.last_row = (path, first + self.window - 1)  # last event of the last slot's last pass
         return tab
+
+    def _buffers(self, P):
+        """The buffers of a window of P batches: ev [B,P,N,4], dt_input [P,B] float64 and, with the hot filter, the masks m_bp
+        [B,P,H,W] and m_pb [P,B,H,W] (None when P = 1: the same layout)."""
+        B, N, dev = self.batch_size, self.window, self.device
+        H, W = self.res
+        ev = torch.empty((B, P, N, 4), dtype=torch.float32, device=dev)
+        dt = torch.empty((P, B), dtype=torch.float64, device=dev)
+        m_bp = torch.empty((B, P, H, W), dtype=torch.float32, device=dev) if self.hot else None
+        m_pb = torch.empty((P, B, H, W), dtype=torch.float32, device=dev) if self.hot and P > 1 else None
+        return ev, dt, m_bp, m_pb
 
     def _launch_cut(self, table_dev, P, ev, dt, m_bp=None, m_pb=None):
         """evf_seq_cut and, with the hot filter, evf_hot_pixels on a job table in device memory (`_job_table`'s layout), into
-        the caller's ev [B,P,N,4], dt [P,B] float64 and masks m_bp [B,P,H,W] / m_pb [P,B,H,W] (either may be None).  No
-        allocation and no host copy: the launches can be captured."""
+        the caller's `_buffers(P)`.  No allocation and no host copy: the launches can be captured."""
         B, N = self.batch_size, self.window
         H, W = self.res
         at = table_dev.data_ptr()
         _lib.call("evf_seq_cut", _lib.ptr(self._xs), _lib.ptr(self._ys), _lib.ptr(self._ts), _lib.ptr(self._ps), self.total_events,
                   at, at + 8 * B * P, B, P, N, H, W, _lib.ptr(ev), _lib.ptr(dt))
         if self.hot:
-            hf = self.config["hot_filter"]
             _lib.call("evf_hot_pixels", _lib.ptr(ev), at + 12 * B * P, _lib.ptr(self._hot_events), _lib.ptr(self._hot_obvs),
-                      _lib.ptr(m_bp), _lib.ptr(m_pb), B, P, N, H, W, int(hf["max_px"]), int(hf["min_obvs"]), float(hf["max_rate"]))
+                      _lib.ptr(m_bp), _lib.ptr(m_pb), B, P, N, H, W, *self._hot_params())
 
     def _cut(self, batches):
-        """P planned batches -> ev [B,P,N,4], dt_input [P,B], hot masks ([B,P,H,W], [P,B,H,W]) or None: one copy of the job
-        table, one evf_seq_cut, one evf_hot_pixels."""
-        B, P, N = self.batch_size, len(batches), self.window
-        H, W = self.res
-        dev = self.device
+        """P planned batches -> fresh `_buffers(P)`, filled: one copy of the job table, one evf_seq_cut, one evf_hot_pixels."""
         t = torch.from_numpy(self._job_table(batches))
-        t = t.pin_memory().to(dev, non_blocking=True)
-        ev = torch.empty((B, P, N, 4), dtype=torch.float32, device=dev)
-        dt = torch.empty((P, B), dtype=torch.float64, device=dev)
-        m_bp = m_pb = None
-        if self.hot:
-            m_bp = torch.empty((B, P, H, W), dtype=torch.float32, device=dev)
-            m_pb = torch.empty((P, B, H, W), dtype=torch.float32, device=dev) if P > 1 else None  # (P = 1: the same layout)
-        self._launch_cut(t, P, ev, dt, m_bp, m_pb)
-        masks = (m_bp, m_pb if m_pb is not None else m_bp.view(P, B, H, W)) if self.hot else None
-        return ev, dt, masks
+        t = t.pin_memory().to(self.device, non_blocking=True)
+        buf = self._buffers(len(batches))
+        self._launch_cut(t, len(batches), *buf)
+        return buf
 
-    def _mask_window(self, passes, m_bp, m_pb):
-        """The hot-pixel masks applied in place to the window buffers behind `passes` (encode_window's dicts)."""
-        B, P = self.batch_size, len(passes)
+    def _window_passes(self, ev, dt, m_bp, m_pb, dt_gt=None):
+        """Filled `_buffers(P)` -> the P batch dicts: the binning (`encode_window`), the hot-pixel masks applied in place to the
+        window buffers, dt_input and dt_gt (rows of `dt_gt` [P,B]; zeros allocated here when None)."""
+        B, P = self.batch_size, ev.shape[1]
         H, W = self.res
-        # network inputs are pass-major ([P,B,C,H,W], one tensor per pass), the loss's mask stack batch-major ([B,P,H,W])
-        cnt = torch.as_strided(passes[0]["event_cnt"], (P * B, 2, H, W), passes[0]["event_cnt"].stride())
-        vox = torch.as_strided(passes[0]["event_voxel"], (P * B, self.num_bins, H, W), passes[0]["event_voxel"].stride())
-        emask = torch.as_strided(passes[0]["event_mask"], (B * P, 1, H, W), (H * W, H * W, W, 1))
-        _lib.call("evf_apply_pixel_mask", _lib.ptr(vox), _lib.ptr(m_pb), P * B, self.num_bins, H, W)
-        _lib.call("evf_apply_pixel_mask", _lib.ptr(cnt), _lib.ptr(m_pb), P * B, 2, H, W)
-        _lib.call("evf_apply_pixel_mask", _lib.ptr(emask), _lib.ptr(m_bp), B * P, 1, H, W)
+        passes = encode_window(ev, self.num_bins, self.res, round_ts=self.round_encoding)
+        if self.hot:
+            m_pb = m_pb if m_pb is not None else m_bp.view(P, B, H, W)
+            # network inputs are pass-major ([P,B,C,H,W], one tensor per pass), the loss's mask stack batch-major ([B,P,H,W])
+            cnt = torch.as_strided(passes[0]["event_cnt"], (P * B, 2, H, W), passes[0]["event_cnt"].stride())
+            vox = torch.as_strided(passes[0]["event_voxel"], (P * B, self.num_bins, H, W), passes[0]["event_voxel"].stride())
+            emask = torch.as_strided(passes[0]["event_mask"], (B * P, 1, H, W), (H * W, H * W, W, 1))
+            _lib.call("evf_apply_pixel_mask", _lib.ptr(vox), _lib.ptr(m_pb), P * B, self.num_bins, H, W)
+            _lib.call("evf_apply_pixel_mask", _lib.ptr(cnt), _lib.ptr(m_pb), P * B, 2, H, W)
+            _lib.call("evf_apply_pixel_mask", _lib.ptr(emask), _lib.ptr(m_bp), B * P, 1, H, W)
+        if dt_gt is None:
+            dt_gt = torch.zeros((P, B), dtype=torch.float64, device=self.device)
+        for p, d in enumerate(passes):
+            d["dt_gt"], d["dt_input"] = dt_gt[p], dt[p]
+        return passes
 
-    def _produce(self, batch):
+    def window_passes(self, batches):
+        """P planned batches -> their batch dicts, cut by ONE launch into one fresh [B,P,N,4] buffer: the allocating twin of
+        `ResidentWindow.launch`."""
+        return self._window_passes(*self._cut(batches))
+
+    def _produce(self, jobs, restarted, done):
         """One planned batch -> the reference's batch dict (dataloader/base.py:248-265)."""
         B = self.batch_size
-        H, W = self.res
-        ev, dt, masks = self._cut([batch])
+        ev, dt, m_bp, _m_pb = self._cut([(jobs, restarted, done)])
         out = encode_event_list(ev.view(B, self.window, 4), self.num_bins, self.res, round_ts=self.round_encoding)
-        if masks is not None:
-            for key, C in (("event_voxel", self.num_bins), ("event_cnt", 2), ("event_mask", 1)):
-                _lib.call("evf_apply_pixel_mask", _lib.ptr(out[key]), _lib.ptr(masks[0]), B, C, H, W)
+        if self.hot:
+            self._mask_batch(out, m_bp)
         out["dt_gt"] = torch.zeros(B, dtype=torch.float64, device=self.device)
         out["dt_input"] = dt[0]
         return out
-
-    def __iter__(self):
-        """The batches of one pass over the files, like `H5Loader.__iter__` with its flags: no reader thread, no device
-        synchronisation."""
-        try:
-            for jobs, (restarted, done) in self.plan_batches():
-                batch = self._produce((jobs, restarted, done))
-                self.new_seq, self.pass_done = restarted, done
-                self.samples += self.batch_size
-                yield batch
-        finally:
-            self._end_pass()
 
     def next_window(self, P):
         """-> (passes, reset): the P batch dicts of the next group of batches on which train_flow.py's loop steps the
@@ -288,30 +241,63 @@ class ResidentLoader(ResidentPlan):
         model, loss and gradients in front of the first of them.  Batches the loop forwards and drops are not returned;
         their hot-pixel observations are made."""
         discarded, group, reset = self.plan_window(P)
-        if self.hot:
-            for at in range(0, len(discarded), 64):  # statistics only; masks and rows are dropped
-                self._cut(discarded[at:at + 64])
-        B = self.batch_size
-        ev, dt, masks = self._cut(group)
-        passes = encode_window(ev, self.num_bins, self.res, round_ts=self.round_encoding)
-        if masks is not None:
-            self._mask_window(passes, *masks)
-        zeros = torch.zeros((P, B), dtype=torch.float64, device=self.device)
-        for p, d in enumerate(passes):
-            d["dt_gt"] = zeros[p]
-            d["dt_input"] = dt[p]
+        self.observe(discarded)
+        passes = self.window_passes(group)
         self.new_seq, self.pass_done = reset, group[-1][2]
         return passes, reset
 
-    # ------------------------------------------------------------------ one value on demand
-    @property
-    def last_proc_timestamp(self):
-        """Timestamp (relative to its file's t0) of the last event handed out: fetched from the arena when asked for."""
-        if self._last_row is not None:
-            self._last_ts = float(self._ts[self._last_row])
-            self._last_row = None
-        return self._last_ts
+    def observe(self, discarded):
+        """Batches the loop forwarded and dropped: their hot-pixel statistics only; masks and rows are dropped."""
+        if self.hot:
+            for at in range(0, len(discarded), 64):
+                self._cut(discarded[at:at + 64])
 
-    @last_proc_timestamp.setter
-    def last_proc_timestamp(self, value):
-        self._last_row, self._last_ts = None, value
+
+class ResidentWindow:
+    """The static buffers of a window of P batches that is cut again and again (a captured graph reads fixed addresses): the
+    loader's `_buffers(P)`, dt_gt zeros [P,B], the job table in device memory -- `_job_table`'s 2*B*P + 1 int64 words, then
+    `extra_words` of the caller's -- and a ring of pinned host tables, each with an event recorded after its copy: the host
+    waits on it before rewriting the table."""
+
+    RING = 4  # pinned job tables in flight (>= 2)
+
+    def __init__(self, loader, P, extra_words=0):
+        self.loader, self.P = loader, int(P)
+        self.static_ev, self.dt, self.m_bp, self.m_pb = loader._buffers(self.P)
+        self.dt_gt = torch.zeros((self.P, loader.batch_size), dtype=torch.float64, device=loader.device)
+        self.base = 2 * loader.batch_size * self.P + 1
+        words = self.base + int(extra_words)
+        self.table_dev = torch.empty(words, dtype=torch.int64, device=loader.device)
+        self.ring = [(torch.empty(words, dtype=torch.int64).pin_memory(), torch.cuda.Event()) for _ in range(self.RING)]
+
+    def stage(self, group, seen):
+        """Step `seen`'s pinned table with `_job_table(group)` in its prefix -> the host view of the extra words, for the
+        caller to fill before `send`."""
+        self._staged = pinned, copied = self.ring[seen % self.RING]
+        copied.synchronize()
+        host = pinned.numpy()
+        host[:self.base] = self.loader._job_table(group)
+        return host[self.base:]
+
+    def send(self):
+        """The staged table to the device on the current stream (non-blocking)."""
+        pinned, copied = self._staged
+        self.table_dev.copy_(pinned, non_blocking=True)
+        copied.record()
+
+    def launch(self):
+        """The cut, the hot-pixel kernel, the binning and the mask launches on the static buffers -> the window's passes.  No
+        allocation beyond `encode_window`'s: it runs under capture."""
+        self.loader._launch_cut(self.table_dev, self.P, self.static_ev, self.dt, self.m_bp, self.m_pb)
+        return self.loader._window_passes(self.static_ev, self.dt, self.m_bp, self.m_pb, self.dt_gt)
+
+
+def zero_states_if(flag_ptr, states):
+    """The tensors of `states` (a model's `state_buffers()`) zero-filled when the int32 at device address `flag_ptr` is not 0:
+    evf_zero_segments_if, 32 segments a launch -- `model.reset_states()` as a node of a captured graph."""
+    flat = [t for st in states if st is not None for t in st if t is not None]
+    for lo in range(0, len(flat), 32):
+        seg = flat[lo:lo + 32]
+        _lib.call("evf_zero_segments_if", flag_ptr, (ctypes.c_void_p * 32)(*[_lib.ptr(t) for t in seg]),
+                  (ctypes.c_int64 * 32)(*[t.numel() * t.element_size() for t in seg]), len(seg))
+

@@ -15,12 +15,12 @@ windows of a batch hold different numbers of events.  Both are settled on the ho
   * With the table on the host, the host knows every window's first event and event count before the launch: the padded
     width of a batch is `max(count)`, and "up to 10 events is an empty window" (dataloader/h5.py:268) is `count = 0`.
 
-`ResidentEvalPlan` is the host-only half (no GPU): H5Loader's constructor, file list, sharding, flags, `reset_sequence`,
-`shuffle`, counters and `_end_pass`, plus `__getitem__`'s cursor step (dataloader/h5.py:243-311) written over the tables.
-`ResidentEvalLoader` adds the arenas and the launches.
+`ResidentEvalPlan` is the host-only half (no GPU): `ResidentCursor` (dataloader/resident_base.py, shared with the `events`
+loader) plus `__getitem__`'s cursor step (dataloader/h5.py:243-311) written over the tables.  `ResidentEvalLoader` adds the
+arenas and the launches.
 
-Layout in device memory: the 13-byte event arena of dataloader/resident.py (`xs`, `ys` uint16, `ts` float64 relative to the
-file's t0, `ps` uint8, one arena per column over all files), and for the mode's group either the ground-truth maps
+Layout in device memory: the 13-byte event arena of `ResidentArena` (dataloader/resident_base.py), and for the mode's group
+either the ground-truth maps
 `[M,2,H,W]` float32 (8 H W bytes per map) or the frames `[M,H,W]` uint8 (H W bytes per frame), all files' in file order, a
 file's in the order of `_Sequence.group()`."""
 
@@ -29,13 +29,13 @@ import torch
 
 from .. import _lib
 from .encodings import binary_search_array, encode_event_list
-from .h5 import H5Loader, open_sequence
-from .resident import FLAG_BITS
+from .h5 import open_sequence
+from .resident_base import ResidentArena, ResidentCursor, read_columns
 
 MODES = ("time", "frames", "gtflow_dt1", "gtflow_dt4")
 
 
-class ResidentEvalPlan(H5Loader):
+class ResidentEvalPlan(ResidentCursor):
     """The host-only half: per slot (sequence file, first event, event count, flip flags, restarted, map index or frame indices,
     dt_gt) of the next input window -- the decisions, counters and `np.random.random()` draws of `H5Loader.__getitem__`, in
     its order.
@@ -66,8 +66,8 @@ class ResidentEvalPlan(H5Loader):
                 raise _lib.EvflowError(f"{path}: index table of {len(self.index[path])} entries for {len(self.queries[path])} "
                                        "boundary queries")
 
-    def _open(self, batch, path):  # (H5Loader opens the slot's file here; a plan notes which one it is and rewinds)
-        self._slot_path[batch] = path
+    def _open(self, batch, path):  # (the plan notes the slot's file and rewinds)
+        super()._open(batch, path)
         self._slot_step[batch] = 0  # windows handed out (or tried) since the file was opened: the row of the time table
 
     # ------------------------------------------------------------------ what the files say
@@ -123,9 +123,6 @@ class ResidentEvalPlan(H5Loader):
         return out
 
     # ------------------------------------------------------------------ the cursor
-    def slot_flags(self, batch):
-        return sum(bit for mech, bit in FLAG_BITS if self._flipped(mech, batch))
-
     def _event_range(self, batch):
         """`get_event_index` + the sub-interval arithmetic of h5.py:254-260 over the index table -> (idx0, idx1)."""
         path = self._slot_path[batch]
@@ -166,13 +163,8 @@ class ResidentEvalPlan(H5Loader):
             if count <= 10:  # very few events: an empty window (h5.py:268)
                 count = 0
             if restart:
-                restarted = self._restarted = True
-                if not self._threaded:
-                    self.new_seq = True
-                self.reset_sequence(batch)
-                self.batch_row[batch] = 0
-                self.batch_idx[batch] = max(self.batch_idx) + 1
-                self._open(batch, self.files[self.batch_idx[batch] % len(self.files)])
+                restarted = True
+                self._restart(batch)
                 continue
             indices, dt_gt = None, 0.0
             if self.mode == "frames":
@@ -185,19 +177,8 @@ class ResidentEvalPlan(H5Loader):
             self._slot_step[batch] += 1
             return path, first, count, self.slot_flags(batch), restarted, indices, float(dt_gt)
 
-    def plan_batches(self):
-        """`H5Loader._host_batches` over the plan: ([job of slot 0, ...], (a slot restarted, wrap-around batch)) until every
-        file has been started once."""
-        while True:
-            self._restarted = False
-            jobs = [self.plan_sample(b) for b in range(self.batch_size)]
-            done = self.seq_num >= len(self.files)
-            yield jobs, (self._restarted, done)
-            if done:
-                return
 
-
-class ResidentEvalLoader(ResidentEvalPlan):
+class ResidentEvalLoader(ResidentArena, ResidentEvalPlan):
     """`resident_bytes`: everything kept in device memory -- 13 bytes per event, 8 H W per ground-truth map or H W per frame
     (a sequence of a few thousand 260 x 346 maps is gigabytes), the hot-pixel statistics.  The absolute timestamp column of the
     one search at construction (8 bytes per event) is freed after it and not counted."""
@@ -207,8 +188,7 @@ class ResidentEvalLoader(ResidentEvalPlan):
         cols, self._cols = self._cols, None
         dev = self.device
         H, W = self.res
-        self._xs, self._ys, self._ts, self._ps = (torch.from_numpy(np.concatenate(c)).to(dev) for c in cols)
-        self.resident_bytes = sum(t.numel() * t.element_size() for t in (self._xs, self._ys, self._ts, self._ps))
+        self._upload(cols)
         self._stack = None  # the mode's maps [M,2,H,W] float32 or frames [M,H,W] uint8
         if self._stamp_group():
             self.stack_offsets, at = {}, 0
@@ -222,10 +202,7 @@ class ResidentEvalLoader(ResidentEvalPlan):
                 a = self._items.pop(path)
                 self._stack[self.stack_offsets[path]:self.stack_offsets[path] + len(a)].copy_(torch.from_numpy(a))
             self.resident_bytes += self._stack.numel() * self._stack.element_size()
-        self.hot = bool(self.config["hot_filter"]["enabled"])
         if self.hot:
-            self._hot_events = torch.zeros((self.batch_size, H, W), dtype=torch.int32, device=dev)
-            self._hot_obvs = torch.zeros(self.batch_size, dtype=torch.int32, device=dev)
             self.resident_bytes += 4 * (self._hot_events.numel() + self._hot_obvs.numel())
 
     # ------------------------------------------------------------------ construction
@@ -234,21 +211,12 @@ class ResidentEvalLoader(ResidentEvalPlan):
         in self._ts_abs until the search), the group's maps or frames (self._items), the metadata of the plan."""
         H, W = self.res
         g = self._stamp_group()
-        xs, ys, ts, ps, ts_abs, meta = [], [], [], [], [], {}
-        self._items = {}
+        self._cols, self._ts_abs, self._items, meta = ([], [], [], []), [], {}, {}
         for path in self.files:
             seq = open_sequence(path)
             names, stamps = self._group_of(seq, path)
-            x, y, p = (np.asarray(seq.events(k)[:]) for k in ("xs", "ys", "ps"))
-            ta = np.asarray(seq.events("ts")[:], dtype=np.float64)
-            t = ta - seq.attrs["t0"]  # get_events, h5.py:210
-            for name, c in (("xs", x), ("ys", y)):
-                if c.size and not (np.all(c == np.floor(c)) and c.min() >= 0 and c.max() <= 65535):
-                    raise _lib.EvflowError(f"{path}: events/{name} holds values that are no integers in [0, 65535]; the "
-                                           "resident arena stores uint16 coordinates: use H5Loader")
-            if p.size and not np.all((p == 0) | (p == 1)):
-                raise _lib.EvflowError(f"{path}: events/ps holds polarities outside {{0, 1}}: use H5Loader")
-            if not len(x):
+            *cols, ta = read_columns(seq, path)
+            if not len(ta):
                 raise _lib.EvflowError(f"{path}: no events: use H5Loader")
             items = []
             for name in names:
@@ -262,20 +230,13 @@ class ResidentEvalLoader(ResidentEvalPlan):
                              np.array(a, dtype=np.float32))
             if items:
                 self._items[path] = np.stack(items)
-            meta[path] = {"events": len(x), "t0": seq.attrs["t0"], "duration": seq.attrs["duration"],
+            meta[path] = {"events": len(ta), "t0": seq.attrs["t0"], "duration": seq.attrs["duration"],
                           "last_ts": seq.events("ts")[-1] - seq.attrs["t0"], "names": names, "stamps": stamps}
             seq.close()
-            xs.append(x.astype(np.uint16))
-            ys.append(y.astype(np.uint16))
-            ts.append(t)
-            ps.append(p.astype(np.uint8))
-            ts_abs.append(ta)
-        self._cols, self._ts_abs = (xs, ys, ts, ps), ts_abs
-        self.offsets, at = {}, 0
-        for path in self.files:
-            self.offsets[path] = at
-            at += meta[path]["events"]
-        self.total_events = at
+            for col, c in zip(self._cols, cols):
+                col.append(c)
+            self._ts_abs.append(ta)
+        self._place({path: m["events"] for path, m in meta.items()})
         return meta
 
     def _search(self):
@@ -320,7 +281,7 @@ class ResidentEvalLoader(ResidentEvalPlan):
                 aux[3 * B + b], aux[4 * B + b] = self.stack_offsets[path] + i0, self.stack_offsets[path] + i1
         return tab
 
-    def _produce(self, jobs):
+    def _produce(self, jobs, _restarted=False, _done=False):
         """One planned batch -> the reference's batch dict (dataloader/base.py:248-265): one copy of the job table, then the
         cut, the hot-pixel filter, the binning, the masks and the gather."""
         B = self.batch_size
@@ -337,17 +298,15 @@ class ResidentEvalLoader(ResidentEvalPlan):
                   self.total_events, at, aux, aux + 4 * B, B, N, H, W, _lib.ptr(ev), _lib.ptr(dt))
         mask = None
         if self.hot:  # (an empty window is an observation too, like create_hot_mask's)
-            hf = self.config["hot_filter"]
             mask = torch.empty((B, H, W), dtype=torch.float32, device=dev)
             _lib.call("evf_hot_pixels", _lib.ptr(ev), aux + 8 * B, _lib.ptr(self._hot_events), _lib.ptr(self._hot_obvs), _lib.ptr(mask),
-                      None, B, 1, N, H, W, int(hf["max_px"]), int(hf["min_obvs"]), float(hf["max_rate"]))
+                      None, B, 1, N, H, W, *self._hot_params())
         out = encode_event_list(ev, self.num_bins, self.res, round_ts=self.round_encoding)
         if npad == 0:  # only padding rows: empty lists, like custom_collate
             out["event_list"] = out["event_list"][:, :0]
             out["event_list_pol_mask"] = out["event_list_pol_mask"][:, :0]
         if mask is not None:
-            for key, C in (("event_voxel", self.num_bins), ("event_cnt", 2), ("event_mask", 1)):
-                _lib.call("evf_apply_pixel_mask", _lib.ptr(out[key]), _lib.ptr(mask), B, C, H, W)
+            self._mask_batch(out, mask)
         out["dt_gt"] = t[B:2 * B].view(torch.float64)
         out["dt_input"] = dt
         if self.mode == "frames":
@@ -359,30 +318,3 @@ class ResidentEvalLoader(ResidentEvalPlan):
             _lib.call("evf_gather_flowmaps", _lib.ptr(self._stack), self.stack_items, aux + 12 * B, aux + 4 * B, B, H, W,
                       _lib.ptr(out["gtflow"]))
         return out
-
-    def __iter__(self):
-        """The batches of one pass over the files, like `H5Loader.__iter__` with its flags: no reader thread, no device
-        synchronisation."""
-        try:
-            for jobs, (restarted, done) in self.plan_batches():
-                batch = self._produce(jobs)
-                self.new_seq, self.pass_done = restarted, done
-                self.samples += self.batch_size
-                yield batch
-        finally:
-            self._end_pass()
-
-    # ------------------------------------------------------------------ one value on demand
-    @property
-    def last_proc_timestamp(self):
-        """Timestamp (relative to its file's t0) of the last event of the last non-empty slice, before the rule that empties
-        windows of up to 10 events (`get_events`): fetched from the arena when asked for."""
-        if self.last_row is not None:
-            path, row = self.last_row
-            self._last_ts = float(self._ts[self.offsets[path] + row])
-            self.last_row = None
-        return self._last_ts
-
-    @last_proc_timestamp.setter
-    def last_proc_timestamp(self, value):
-        self.last_row, self._last_ts = None, value

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .dataloader.encodings import encode_window
+from .dataloader.resident import ResidentWindow, zero_states_if
 from .utils.iwe import compute_pol_iwe
 
 
@@ -124,8 +124,6 @@ class ResidentEvalStep:
         out = stepper.results()
     """
 
-    RING = 4  # pinned tables in flight (>= 2)
-
     def __init__(self, model, criteria, names, loader, P, rows, flow_scaling, overwrite_intermediate=False, warmup=2,
                  replay=True, per_sequence=False):
         for name in ("plan_eval_steps", "_job_table", "_launch_cut"):
@@ -140,24 +138,14 @@ class ResidentEvalStep:
         self.P, self.rows, self.replay = int(P), int(rows), bool(replay)
         self.flow_scaling, self.overwrite = flow_scaling, bool(overwrite_intermediate)
         self.warmup, self.seen = max(int(warmup), 2), 0
-        B, N, dev = loader.batch_size, loader.window, loader.device
-        H, W = loader.res
-        P, K = self.P, len(self.names)
+        B, P, K = loader.batch_size, self.P, len(self.names)
         self.B, self.K = B, K
-        self.static_ev = torch.empty((B, P, N, 4), dtype=torch.float32, device=dev)
-        self.dt = torch.empty((P, B), dtype=torch.float64, device=dev)
-        self.dt_gt = torch.zeros((P, B), dtype=torch.float64, device=dev)
-        self.m_bp = torch.empty((B, P, H, W), dtype=torch.float32, device=dev) if loader.hot else None
-        self.m_pb = torch.empty((P, B, H, W), dtype=torch.float32, device=dev) if loader.hot and P > 1 else None
-        self.base = 2 * B * P + 1  # int64 words of ResidentLoader._job_table
-        self.words = self.base + (P + 1) // 2 + 1
-        self.table_dev = torch.empty(self.words, dtype=torch.int64, device=dev)
-        self._reset_flags = self.table_dev.data_ptr() + 8 * self.base  # P int32 words
-        self._row_word = self.table_dev.data_ptr() + 8 * (self.words - 1)
+        extra = (P + 1) // 2 + 1  # behind the job table: P int32 pass_reset words (a whole int64 word), the row word
+        self.window = ResidentWindow(loader, P, extra_words=extra)
+        self._reset_flags = self.window.table_dev.data_ptr() + 8 * self.window.base
+        self._row_word = self._reset_flags + 8 * (extra - 1)
         self.row_floats = row_layout(K, B, P)
-        self.log = torch.full((max(self.rows, 1), self.row_floats), float("nan"), dtype=torch.float32, device=dev)
-        # each pinned table has an event recorded after its copy; the host waits on it before rewriting the table
-        self.ring = [(torch.zeros(self.words, dtype=torch.int64).pin_memory(), torch.cuda.Event()) for _ in range(self.RING)]
+        self.log = torch.full((max(self.rows, 1), self.row_floats), float("nan"), dtype=torch.float32, device=loader.device)
         self.stream = torch.cuda.Stream()
         self.graphs = None
         self.tail_sharp = []  # 0-d tensors of the tail passes
@@ -165,22 +153,16 @@ class ResidentEvalStep:
         self.stats = {"eager": 0, "replayed": 0, "replayed_reset": 0, "graph_a": 0, "graph_b": 0, "tail_passes": 0}
 
     # ------------------------------------------------------------------ launches
-    def _zero_states(self, p):
-        """The state tensors the next pass reads, cleared under pass p's reset word."""
-        flat = [t for st in self.model.state_buffers() if st is not None for t in st if t is not None]
-        for lo in range(0, len(flat), 32):
-            seg = flat[lo:lo + 32]
-            _lib.call("evf_zero_segments_if", self._reset_flags + 4 * p, (ctypes.c_void_p * 32)(*[_lib.ptr(t) for t in seg]),
-                      (ctypes.c_int64 * 32)(*[t.numel() * t.element_size() for t in seg]), len(seg))
-
     def _passes(self, passes, pass_reset):
         """Forward, image of warped events, sharpness scalar and association of every pass -> (sharpness scalars, last flow).
-        `pass_reset` None: a captured graph, the state is zero-filled under the table's words; else the eager reset."""
+        `pass_reset` None: a captured graph, the state tensors the pass reads are zero-filled under its word of the table; else
+        the eager reset."""
         res = self.loader.res
         sharp, x = [], None
         for p, d in enumerate(passes):
+            d.setdefault("event_voxel", None)
             if pass_reset is None:
-                self._zero_states(p)
+                zero_states_if(self._reset_flags + 4 * p, self.model.state_buffers())
             elif pass_reset[p]:
                 self.model.reset_states()
             if p == self.P - 1:
@@ -195,14 +177,8 @@ class ResidentEvalStep:
 
     def _window(self, pass_reset):
         """The launches of one evaluated window on the static buffers (see the class) -> its passes."""
-        L, P, B = self.loader, self.P, self.B
-        L._launch_cut(self.table_dev, P, self.static_ev, self.dt, self.m_bp, self.m_pb)
-        passes = encode_window(self.static_ev, L.num_bins, L.res, round_ts=L.round_encoding)
-        if L.hot:
-            L._mask_window(passes, self.m_bp, self.m_pb if self.m_pb is not None else self.m_bp.view(P, -1, *L.res))
-        for p, d in enumerate(passes):
-            d["dt_gt"], d["dt_input"] = self.dt_gt[p], self.dt[p]
-            d.setdefault("event_voxel", None)
+        B = self.B
+        passes = self.window.launch()
         sharp, x = self._passes(passes, pass_reset)
         src, off, cnt = [], [], []
         for k, metric in enumerate(self.criteria):
@@ -242,7 +218,6 @@ class ResidentEvalStep:
     # ------------------------------------------------------------------ steps
     def step(self, group, pass_reset):
         """One evaluated window: the P batches of `group` with their `pass_reset` flags (a triple of `plan_eval_steps`)."""
-        L = self.loader
         if len(group) != self.P or len(pass_reset) != self.P:
             raise _lib.EvflowError(f"ResidentEvalStep: a window of {len(group)} batches, built for {self.P}")
         if self.stats["tail_passes"]:
@@ -253,15 +228,11 @@ class ResidentEvalStep:
         cur = torch.cuda.current_stream()
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream), torch.no_grad():
-            pinned, copied = self.ring[self.seen % len(self.ring)]
-            copied.synchronize()
-            host = pinned.numpy()
-            host[:self.base] = L._job_table(group)
-            host[self.base:self.words - 1] = 0
-            host[self.base:self.words - 1].view(np.int32)[:self.P] = [1 if r else 0 for r in pass_reset]
-            host[self.words - 1] = row
-            self.table_dev.copy_(pinned, non_blocking=True)
-            copied.record(self.stream)
+            extra = self.window.stage(group, self.seen)
+            extra[:-1] = 0
+            extra[:-1].view(np.int32)[:self.P] = [1 if r else 0 for r in pass_reset]
+            extra[-1] = row
+            self.window.send()
             if not self.replay or self.seen < self.warmup:
                 self._window(list(pass_reset))
                 self.stats["eager"] += 1
@@ -284,7 +255,6 @@ class ResidentEvalStep:
     def step_tail(self, group, pass_reset):
         """The fewer than P batches behind the last whole window: forwarded and associated like every batch, never evaluated
         (the loop ends before `window_eval` events are collected); their sharpness scalars count."""
-        L = self.loader
         if len(group) >= self.P or len(pass_reset) != len(group):
             raise _lib.EvflowError(f"ResidentEvalStep: a tail of {len(group)} batches (fewer than {self.P} expected)")
         if not group:
@@ -292,15 +262,7 @@ class ResidentEvalStep:
         cur = torch.cuda.current_stream()
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream), torch.no_grad():
-            ev, dt, masks = L._cut(group)
-            passes = encode_window(ev, L.num_bins, L.res, round_ts=L.round_encoding)
-            if masks is not None:
-                L._mask_window(passes, *masks)
-            zeros = torch.zeros((len(group), self.B), dtype=torch.float64, device=L.device)
-            for p, d in enumerate(passes):
-                d["dt_gt"], d["dt_input"] = zeros[p], dt[p]
-                d.setdefault("event_voxel", None)
-            sharp, _x = self._passes(passes, list(pass_reset))
+            sharp, _x = self._passes(self.loader.window_passes(group), list(pass_reset))
             self.tail_sharp += sharp
             self.stats["tail_passes"] += len(group)
         cur.wait_stream(self.stream)

@@ -14,7 +14,8 @@ import weakref
 import torch
 
 from . import _lib
-from .dataloader.encodings import encode_event_list, encode_event_lists, encode_window
+from .dataloader.encodings import encode_event_list, encode_event_lists
+from .dataloader.resident import ResidentWindow, zero_states_if
 from .models import hip_ops
 
 
@@ -504,50 +505,18 @@ class ResidentWindowStep(GraphedWindowStep):
         loss, info = stepper.step()      # 0-d loss tensor (no host sync); info: reset, n_discarded, done
     """
 
-    RING = 4  # pinned job tables in flight (>= 2)
-
     def __init__(self, model, loss_function, optimizer, loader, P, warmup=2, replay=True):
         for name in ("plan_window", "_job_table", "_launch_cut"):
             if not hasattr(loader, name):
                 raise _lib.EvflowError("ResidentWindowStep needs a ResidentLoader (the windows are cut out of its device-resident arena)")
         super().__init__(model, loss_function, optimizer, loader.num_bins, loader.res, dp=None, warmup=warmup)
         self.loader, self.P, self.replay = loader, int(P), bool(replay)
-        B, N, dev = loader.batch_size, loader.window, loader.device
-        H, W = loader.res
-        P = self.P
-        self.static_ev = torch.empty((B, P, N, 4), dtype=torch.float32, device=dev)
-        self.dt = torch.empty((P, B), dtype=torch.float64, device=dev)
-        self.dt_gt = torch.zeros((P, B), dtype=torch.float64, device=dev)
-        self.m_bp = torch.empty((B, P, H, W), dtype=torch.float32, device=dev) if loader.hot else None
-        self.m_pb = torch.empty((P, B, H, W), dtype=torch.float32, device=dev) if loader.hot and P > 1 else None
-        words = 2 * B * P + 1  # ResidentLoader._job_table: first | flags, slot reset | window reset
-        self.table_dev = torch.empty(words, dtype=torch.int64, device=dev)
-        self._reset_flag = self.table_dev.data_ptr() + 16 * B * P
-        # each pinned table has an event recorded after its copy; the host waits on it before rewriting the table
-        self.ring = [(torch.empty(words, dtype=torch.int64).pin_memory(), torch.cuda.Event()) for _ in range(self.RING)]
+        self.window = ResidentWindow(loader, self.P)
+        # ResidentLoader._job_table: first | flags, slot reset | window reset
+        self._reset_flag = self.window.table_dev.data_ptr() + 16 * loader.batch_size * self.P
         self.passes = None  # the window buffers of the last step (views of static tensors once the graphs replay)
         self.stats = {"eager": 0, "replayed": 0, "replayed_reset": 0, "replayed_discarded": 0, "discarded": 0,
                       "graph_a": 0, "graph_b": 0}
-
-    def _window(self, states=None):
-        """The launches of a window in front of `train_window`, on the static buffers -> its passes.  `states`: the state
-        tensors to clear under the table's reset flag first (a captured graph; the eager step drops the state instead)."""
-        import ctypes
-
-        L = self.loader
-        if states is not None:
-            flat = [t for st in states if st is not None for t in st if t is not None]
-            for lo in range(0, len(flat), 32):
-                seg = flat[lo:lo + 32]
-                _lib.call("evf_zero_segments_if", self._reset_flag, (ctypes.c_void_p * 32)(*[_lib.ptr(t) for t in seg]),
-                          (ctypes.c_int64 * 32)(*[t.numel() * t.element_size() for t in seg]), len(seg))
-        L._launch_cut(self.table_dev, self.P, self.static_ev, self.dt, self.m_bp, self.m_pb)
-        passes = encode_window(self.static_ev, L.num_bins, L.res, round_ts=L.round_encoding)
-        if L.hot:
-            L._mask_window(passes, self.m_bp, self.m_pb if self.m_pb is not None else self.m_bp.view(self.P, -1, *L.res))
-        for p, d in enumerate(passes):
-            d["dt_gt"], d["dt_input"] = self.dt_gt[p], self.dt[p]
-        return passes
 
     def _capture(self):
         home = self.model.state_buffers()
@@ -560,7 +529,9 @@ class ResidentWindowStep(GraphedWindowStep):
                 self.model.final_states_into(home)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=self.stream, capture_error_mode="global"):
-                passes = self._window(states=self.model.state_buffers())
+                # (the loop's `model.reset_states()`: the state THIS graph reads, cleared under the table's reset word)
+                zero_states_if(self._reset_flag, self.model.state_buffers())
+                passes = self.window.launch()
                 loss = train_window(self.model, self.lossf, self.opt, passes)
             self.graphs.append((g, loss, self.model.state_buffers(), passes))
 
@@ -574,18 +545,13 @@ class ResidentWindowStep(GraphedWindowStep):
         cur = torch.cuda.current_stream()
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
-            if L.hot:
-                for at in range(0, len(discarded), 64):  # forwarded and dropped by the loop: hot-pixel statistics only
-                    L._cut(discarded[at:at + 64])
-            pinned, copied = self.ring[self.seen % len(self.ring)]
-            copied.synchronize()
-            pinned.numpy()[:] = L._job_table(group)
-            self.table_dev.copy_(pinned, non_blocking=True)
-            copied.record(self.stream)
+            L.observe(discarded)
+            self.window.stage(group, self.seen)
+            self.window.send()
             if not self.replay or self.seen < self.warmup:
                 if reset:
                     self.model.reset_states()
-                self.passes = self._window()
+                self.passes = self.window.launch()
                 loss = train_window(self.model, self.lossf, self.opt, self.passes)
                 self.stats["eager"] += 1
             else:

@@ -48,6 +48,54 @@ def _same_batch(a, b, what):
         assert a[k].is_cuda and a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and torch.equal(a[k], b[k]), (what, k)
 
 
+@pytest.mark.parametrize("N", [11, 257])  # the smallest window the loader admits / past one block of 256 threads
+def test_seq_cut_is_the_host_formatting(N):
+    """evf_seq_cut through the C ABI on an arena of 700 events at 15 x 21, B = 2, P = 3 (job j = b * P + p), every flip flag on
+    every job: rows bit for bit the loader's host functions on the host slice, dt[p, b] the slice's span; the last readable
+    window; a window one event past the arena and a negative first come back as zero rows with dt = 0."""
+    from event_flow_amd.dataloader.base import BaseDataLoader
+
+    rng = np.random.Generator(np.random.PCG64(8))
+    n, (H, W), B, P = 700, (15, 21), 2, 3
+    xs, ys, ts, ps = cols = (rng.integers(0, W, n).astype(np.uint16), rng.integers(0, H, n).astype(np.uint16),
+                             np.sort(rng.random(n)) * 0.3 + 2.0, rng.integers(0, 2, n).astype(np.uint8))
+    dev = [torch.from_numpy(c).cuda() for c in cols]
+    first = [0, 40, n - N, n - N + 1, -1, 333]
+    first_dev = torch.tensor(first, dtype=torch.int64).cuda()
+    host = BaseDataLoader.__new__(BaseDataLoader)
+    host.res = (H, W)
+    for sweep in range(8):
+        flags = [(sweep + j) & 7 for j in range(B * P)]
+        flags_dev = torch.tensor(flags, dtype=torch.int32).cuda()
+        ev = torch.full((B, P, N, 4), 9.0, dtype=torch.float32, device="cuda")
+        dt = torch.full((P, B), 9.0, dtype=torch.float64, device="cuda")
+        _lib.call("evf_seq_cut", *(_lib.ptr(c) for c in dev), n, _lib.ptr(first_dev), _lib.ptr(flags_dev), B, P, N, H, W,
+                  _lib.ptr(ev), _lib.ptr(dt))
+        ev, dt = ev.cpu().numpy(), dt.cpu().numpy()
+        for j, (f, fl) in enumerate(zip(first, flags)):
+            b, p = divmod(j, P)
+            if f < 0 or f > n - N:
+                assert not ev[b, p].any() and dt[p, b] == 0.0, (sweep, j)
+                continue
+            host.batch_augmentation = {m: [bool(fl & bit)] for m, bit in zip(FLIPS, (1, 2, 4))}
+            x, y, t, pol = host.event_formatting(xs[f:f + N], ys[f:f + N], ts[f:f + N], ps[f:f + N])
+            x, y, pol = host.augment_events(x, y, pol, 0)
+            rows = host.create_list_encoding(x, y, t, pol).T
+            assert np.array_equal(ev[b, p].view(np.uint32), rows.view(np.uint32)), (sweep, j)  # bit for bit
+            assert dt[p, b] == ts[f + N - 1] - ts[f], (sweep, j)
+    # bad arguments are refused before a launch; an empty arena is not one (every job is padding)
+    out_ev, out_dt = torch.zeros((1, 1, 4, 4), dtype=torch.float32, device="cuda"), torch.zeros((1, 1), dtype=torch.float64, device="cuda")
+    ok = [_lib.ptr(c) for c in dev] + [n, _lib.ptr(first_dev), _lib.ptr(flags_dev), 1, 1, 4, H, W, _lib.ptr(out_ev), _lib.ptr(out_dt)]
+    assert _lib.raw("evf_seq_cut", *ok) == 0
+    assert _lib.raw("evf_seq_cut", *ok[:4], 0, *ok[5:]) == 0
+    for at, bad in ((0, None), (1, None), (2, None), (3, None), (4, -1), (5, None), (6, None), (7, 0), (7, 65536), (8, 0), (9, 0),
+                    (10, 0), (11, 0), (12, None), (13, None)):
+        args = list(ok)
+        args[at] = bad
+        assert _lib.raw("evf_seq_cut", *args) != 0, at
+    torch.cuda.synchronize()
+
+
 def test_batches_match_the_reference_collate(tmp_path):
     """Fixture G13 (the reference's loader code: flips and hot-pixel filter on) at the bars of tests/test_gpu_loader.py."""
     g, (H, W, win, nwin, nb) = _g13_files(tmp_path)
