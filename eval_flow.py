@@ -4,7 +4,8 @@ exactly as the reference loop does (association per input window, metric once `w
 No MLflow / visualiser; results are printed as JSON.
 
   python eval_flow.py --config configs/eval_flow.yml --train-config configs/train_SNN.yml --synthetic [--weights model.pth]
-  python eval_flow.py ... --resident --graphed [--per-sequence]   # data.mode events: a graph launch per evaluated window
+  python eval_flow.py ... --resident --graphed [--per-sequence]   # data.mode events: a graph launch per evaluated window;
+                                                                  # gtflow_dt1 / gtflow_dt4 with metrics [AEE]: one per pass
 """
 
 import argparse
@@ -15,7 +16,7 @@ import torch
 
 from event_flow_amd import _lib
 from event_flow_amd.configs.parser import YAMLParser
-from event_flow_amd.evaluate import PerSequence, ResidentEvalStep, graphed_refusal, slot_files
+from event_flow_amd.evaluate import PerSequence, ResidentAEEStep, ResidentEvalStep, graphed_refusal, slot_files
 from event_flow_amd.loss import flow as metrics_mod
 from event_flow_amd.models.model import MODELS
 from event_flow_amd.utils.iwe import compute_pol_iwe
@@ -96,6 +97,8 @@ def test(args, config_parser, graphed_replay=True):
         from event_flow_amd.utils.visualization import Visualization
 
         vis = Visualization(config, eval_id=0, path_results=args.store.rstrip("/") + "/")
+    if graphed and config["data"]["mode"] != "events":  # (graphed_refusal: AEE alone on ground-truth windows)
+        return _test_graphed_aee(config, model, data, per_sequence, graphed_replay)
     if graphed:
         return _test_graphed(config, model, criteria, names, data, per_sequence, graphed_replay)
     per_seq = PerSequence() if per_sequence else None
@@ -180,6 +183,24 @@ def _test_graphed(config, model, criteria, names, data, per_sequence, replay):
     return out
 
 
+def _test_graphed_aee(config, model, data, per_sequence, replay):
+    """The loop above for AEE alone in `data.mode` gtflow_dt1 / gtflow_dt4 on the resident loader, a PASS per step: one table
+    copy and one graph launch each; which passes evaluate (the `idx_AEE` rule), how many there are and the width of the
+    replayed buffers come from the host-only plan, the results are read once at the end (evaluate.ResidentAEEStep)."""
+    plan = list(data.plan_eval_passes())
+    capacity = max([job[2] for jobs, _restarted, _evaluate in plan for job in jobs] + [1])
+    evaluations = sum(1 for _jobs, _restarted, evaluate in plan if evaluate)
+    stepper = ResidentAEEStep(model, data, len(plan), evaluations, capacity, config["metrics"]["flow_scaling"], replay=replay,
+                              per_sequence=per_sequence)
+    model.reset_states()
+    for jobs, restarted, evaluate in plan:
+        stepper.step(jobs, restarted, evaluate)
+    out = {"model": config["model"]["name"], **stepper.results(),
+           "graphed": {**stepper.stats, "passes": stepper.seen, "evaluations": stepper.evaluated, "capacity": capacity}}
+    print(json.dumps(out))
+    return out
+
+
 if __name__ == "__main__":
     parser = argparse.ArgumentParser()
     parser.add_argument("--config", default="configs/eval_flow.yml")
@@ -194,7 +215,8 @@ if __name__ == "__main__":
     parser.add_argument("--graphed", action="store_true",
                         help="with --resident and data.mode events: every evaluated window (window_eval events) is one job-table "
                              "copy plus one hipGraph launch, results logged on the device and read once at the end (fused "
-                             "LIF / PLIF / XLIF / ALIF FireNets; FWL / RSAT)")
+                             "LIF / PLIF / XLIF / ALIF FireNets; FWL / RSAT); with data.mode gtflow_dt1 / gtflow_dt4 and metrics.name "
+                             "[AEE]: every PASS is one job-table copy plus one hipGraph launch, AEE reduced on the device")
     parser.add_argument("--per-sequence", action="store_true", dest="per_sequence",
                         help="also report every metric per sequence file (\"per_sequence\": {file: {metric: mean, \"it\": n}})")
     parser.add_argument("--store", default="", help="directory that receives results/eval_0/<sequence>/{events,flow,iwe,...}/*.png")

@@ -58,6 +58,10 @@ SIGNATURES = {
     "evf_zero_segments_if": [P, P, P, I, P],
     # result log of a replayed evaluation step: device row word, nrows, log, row_floats, host arrays src / offset / n, nseg
     "evf_store_segments_at": [P, L, P, L, P, P, P, I, P],
+    # the AEE of one pass into a row of a device log: flow, gt, mask, dt_gt, dt_input (device doubles), B, H, W, flow_scaling,
+    # device row word, nrows, log, row_floats, offset, ws, ws_floats  /  the stripes per sample that size ws (B * S * 3 floats)
+    "evf_aee_at": [P, P, P, P, P, I, I, I, F, P, L, P, L, I, P, L, P],
+    "evf_aee_at_stripes": [I, I],
     # device-resident evaluation (dataloader/resident_eval.py): ts, total, seg_begin, seg_len, query, Q, out
     "evf_ts_search": [P, L, P, P, P, L, P, P],
     # arena columns, total, first, count, flags, J, Npad, H, W, ev, dt_input

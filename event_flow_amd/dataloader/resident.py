@@ -6,7 +6,8 @@ evaluation loader: dataloader/resident_base.py.
 Only `data.mode: events` (the training mode): there the next window of a slot is index arithmetic on the sequence LENGTHS,
 so the host decides everything without a device value.  That decision is `ResidentPlan` -- `ResidentCursor` plus the cursor
 step of dataloader/h5.py:244-279,310 written over lengths.  It needs no GPU.  `ResidentLoader` adds the arena and the launches,
-`ResidentWindow` the static buffers of a window that is cut again and again (the graph-replayed steppers).
+`ResidentWindow` the static buffers of a window that is cut again and again (the graph-replayed steppers), over `StaticTable`,
+the job table at a fixed device address with its ring of pinned host copies (shared with the evaluation loader's window).
 
 Layout in device memory: one arena per column over all files, `xs`, `ys` uint16, `ts` float64 RELATIVE to its file's t0
 (subtracted on the host in float64 exactly like `get_events`), `ps` uint8 -- 13 bytes per event -- and int64 offsets."""
@@ -253,19 +254,15 @@ class ResidentLoader(ResidentArena, ResidentPlan):
                 self._cut(discarded[at:at + 64])
 
 
-class ResidentWindow:
-    """The static buffers of a window of P batches that is cut again and again (a captured graph reads fixed addresses): the
-    loader's `_buffers(P)`, dt_gt zeros [P,B], the job table in device memory -- `_job_table`'s 2*B*P + 1 int64 words, then
-    `extra_words` of the caller's -- and a ring of pinned host tables, each with an event recorded after its copy: the host
-    waits on it before rewriting the table."""
+class StaticTable:
+    """A job table at a fixed device address that is rewritten step after step (a captured graph reads fixed addresses): the
+    `base` int64 words of the loader's `_job_table`, then `extra_words` of the caller's, and a ring of pinned host tables, each
+    with an event recorded after its copy: the host waits on it before rewriting the table."""
 
     RING = 4  # pinned job tables in flight (>= 2)
 
-    def __init__(self, loader, P, extra_words=0):
-        self.loader, self.P = loader, int(P)
-        self.static_ev, self.dt, self.m_bp, self.m_pb = loader._buffers(self.P)
-        self.dt_gt = torch.zeros((self.P, loader.batch_size), dtype=torch.float64, device=loader.device)
-        self.base = 2 * loader.batch_size * self.P + 1
+    def __init__(self, loader, base, extra_words=0):
+        self.loader, self.base = loader, int(base)
         words = self.base + int(extra_words)
         self.table_dev = torch.empty(words, dtype=torch.int64, device=loader.device)
         self.ring = [(torch.empty(words, dtype=torch.int64).pin_memory(), torch.cuda.Event()) for _ in range(self.RING)]
@@ -284,6 +281,17 @@ class ResidentWindow:
         pinned, copied = self._staged
         self.table_dev.copy_(pinned, non_blocking=True)
         copied.record()
+
+
+class ResidentWindow(StaticTable):
+    """The static buffers of a window of P batches that is cut again and again: the loader's `_buffers(P)`, dt_gt zeros [P,B]
+    and `StaticTable` over `_job_table`'s 2*B*P + 1 int64 words."""
+
+    def __init__(self, loader, P, extra_words=0):
+        self.P = int(P)
+        self.static_ev, self.dt, self.m_bp, self.m_pb = loader._buffers(self.P)
+        self.dt_gt = torch.zeros((self.P, loader.batch_size), dtype=torch.float64, device=loader.device)
+        super().__init__(loader, 2 * loader.batch_size * self.P + 1, extra_words)
 
     def launch(self):
         """The cut, the hot-pixel kernel, the binning and the mask launches on the static buffers -> the window's passes.  No

@@ -30,6 +30,7 @@ import torch
 from .. import _lib
 from .encodings import binary_search_array, encode_event_list
 from .h5 import open_sequence
+from .resident import StaticTable
 from .resident_base import ResidentArena, ResidentCursor, read_columns
 
 MODES = ("time", "frames", "gtflow_dt1", "gtflow_dt4")
@@ -177,6 +178,33 @@ class ResidentEvalPlan(ResidentCursor):
             self._slot_step[batch] += 1
             return path, first, count, self.slot_flags(batch), restarted, indices, float(dt_gt)
 
+    def plan_eval_passes(self):
+        """ONE pass over the files as eval_flow.py's loop meets it in a ground-truth mode with AEE: the batches of
+        `plan_batches()` up to, not including, the wrap-around (`done`) batch -- the loop breaks on that one before forwarding
+        it -- as (jobs, restarted, evaluate) per batch.  `restarted`: the loop's `model.reset_states()` in front of the pass;
+        `evaluate`: the loop's `idx_AEE` rule over host values -- a batch whose slot-0 dt_gt <= 0 neither counts nor evaluates,
+        every other one counts, and the batch on which the counter reaches round(1 / window) evaluates and returns it to 0
+        (reference eval_flow.py:169-176).  The loader's flags, sample counter and end-of-pass bookkeeping move as in
+        `__iter__`, np.random is drawn from exactly as there."""
+        if self.mode not in ("gtflow_dt1", "gtflow_dt4"):
+            raise _lib.EvflowError(f"plan_eval_passes: AEE is evaluated on ground-truth windows (gtflow_dt1 / gtflow_dt4), not in "
+                                   f"data.mode '{self.mode}'")
+        aee_every = int(np.round(1.0 / self.window))
+        counted = 0
+        try:
+            for jobs, (restarted, done) in self.plan_batches():
+                self._delivered(restarted, done)
+                if done:
+                    break
+                evaluate = False
+                if not jobs[0][6] <= 0.0:
+                    counted += 1
+                    if counted == aee_every:
+                        evaluate, counted = True, 0
+                yield jobs, restarted, evaluate
+        finally:
+            self._end_pass()
+
 
 class ResidentEvalLoader(ResidentArena, ResidentEvalPlan):
     """`resident_bytes`: everything kept in device memory -- 13 bytes per event, 8 H W per ground-truth map or H W per frame
@@ -284,37 +312,77 @@ class ResidentEvalLoader(ResidentArena, ResidentEvalPlan):
     def _produce(self, jobs, _restarted=False, _done=False):
         """One planned batch -> the reference's batch dict (dataloader/base.py:248-265): one copy of the job table, then the
         cut, the hot-pixel filter, the binning, the masks and the gather."""
-        B = self.batch_size
-        H, W = self.res
-        dev = self.device
         npad = max(j[2] for j in jobs)  # known on the host: no device value decides a shape
         N = max(npad, 1)
-        t = torch.from_numpy(self._job_table(jobs)).pin_memory().to(dev, non_blocking=True)
-        at = t.data_ptr()
-        aux = at + 16 * B
-        ev = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
-        dt = torch.empty(B, dtype=torch.float64, device=dev)
-        _lib.call("evf_seq_cut_ragged", _lib.ptr(self._xs), _lib.ptr(self._ys), _lib.ptr(self._ts), _lib.ptr(self._ps),
-                  self.total_events, at, aux, aux + 4 * B, B, N, H, W, _lib.ptr(ev), _lib.ptr(dt))
-        mask = None
-        if self.hot:  # (an empty window is an observation too, like create_hot_mask's)
-            mask = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-            _lib.call("evf_hot_pixels", _lib.ptr(ev), aux + 8 * B, _lib.ptr(self._hot_events), _lib.ptr(self._hot_obvs), _lib.ptr(mask),
-                      None, B, 1, N, H, W, *self._hot_params())
-        out = encode_event_list(ev, self.num_bins, self.res, round_ts=self.round_encoding)
+        t = torch.from_numpy(self._job_table(jobs)).pin_memory().to(self.device, non_blocking=True)
+        out = self._launch(t, N, *self._buffers(N))
         if npad == 0:  # only padding rows: empty lists, like custom_collate
             out["event_list"] = out["event_list"][:, :0]
             out["event_list_pol_mask"] = out["event_list_pol_mask"][:, :0]
-        if mask is not None:
+        return out
+
+    def _buffers(self, N):
+        """The buffers of a batch of width N: ev [B,N,4], dt_input [B] float64, with the hot filter the mask [B,H,W], and the
+        mode's gathered maps [B,2,H,W] float32 or frames [B,2,H,W] uint8 (None in `time` mode)."""
+        B, dev = self.batch_size, self.device
+        H, W = self.res
+        ev = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
+        dt = torch.empty(B, dtype=torch.float64, device=dev)
+        mask = torch.empty((B, H, W), dtype=torch.float32, device=dev) if self.hot else None
+        items = None
+        if self._stack is not None:
+            items = torch.empty((B, 2, H, W), dtype=torch.uint8 if self.mode == "frames" else torch.float32, device=dev)
+        return ev, dt, mask, items
+
+    def _launch(self, table_dev, N, ev, dt, mask, items):
+        """The launches of one batch on a job table in device memory (`_job_table`'s layout) into the caller's `_buffers(N)`:
+        the ragged cut (rows behind a slot's count are zero, whatever N), the hot-pixel kernel with its reset column, the
+        binning, the masks and the gather -> the batch dict, `dt_gt` a view of the table.  No allocation beyond
+        `encode_event_list`'s and no host copy: the launches can be captured."""
+        B = self.batch_size
+        H, W = self.res
+        at = table_dev.data_ptr()
+        aux = at + 16 * B
+        _lib.call("evf_seq_cut_ragged", _lib.ptr(self._xs), _lib.ptr(self._ys), _lib.ptr(self._ts), _lib.ptr(self._ps),
+                  self.total_events, at, aux, aux + 4 * B, B, N, H, W, _lib.ptr(ev), _lib.ptr(dt))
+        if self.hot:  # (an empty window is an observation too, like create_hot_mask's)
+            _lib.call("evf_hot_pixels", _lib.ptr(ev), aux + 8 * B, _lib.ptr(self._hot_events), _lib.ptr(self._hot_obvs), _lib.ptr(mask),
+                      None, B, 1, N, H, W, *self._hot_params())
+        out = encode_event_list(ev, self.num_bins, self.res, round_ts=self.round_encoding)
+        if self.hot:
             self._mask_batch(out, mask)
-        out["dt_gt"] = t[B:2 * B].view(torch.float64)
+        out["dt_gt"] = table_dev[B:2 * B].view(torch.float64)
         out["dt_input"] = dt
         if self.mode == "frames":
-            out["frames"] = torch.empty((B, 2, H, W), dtype=torch.uint8, device=dev)
+            out["frames"] = items
             _lib.call("evf_gather_frames", _lib.ptr(self._stack), self.stack_items, aux + 12 * B, aux + 16 * B, aux + 4 * B, B, H, W,
-                      _lib.ptr(out["frames"]))
+                      _lib.ptr(items))
         elif self._stack is not None:
-            out["gtflow"] = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev)
+            out["gtflow"] = items
             _lib.call("evf_gather_flowmaps", _lib.ptr(self._stack), self.stack_items, aux + 12 * B, aux + 4 * B, B, H, W,
-                      _lib.ptr(out["gtflow"]))
+                      _lib.ptr(items))
         return out
+
+
+class ResidentEvalWindow(StaticTable):
+    """The static buffers of ONE batch of a fixed width that is produced again and again (a captured graph reads fixed
+    addresses): the loader's `_buffers(capacity)`, the job table in device memory -- `_job_table`'s 2 B + ceil(5 B / 2) int64
+    words, then `extra_words` of the caller's -- and `StaticTable`'s ring of pinned host tables.  `capacity`: at least the
+    largest event count of any job that will be staged; the rows behind a slot's count are zero, so the padding is invisible
+    to the binning, the masks and the hot-pixel statistics."""
+
+    def __init__(self, loader, capacity, extra_words=0):
+        self.capacity = max(int(capacity), 1)
+        self.buffers = loader._buffers(self.capacity)
+        B = loader.batch_size
+        super().__init__(loader, 2 * B + (5 * B + 1) // 2, extra_words)
+
+    def stage(self, jobs, seen):
+        most = max(j[2] for j in jobs)
+        if most > self.capacity:
+            raise _lib.EvflowError(f"ResidentEvalWindow: a window of {most} events in buffers of {self.capacity}")
+        return super().stage(jobs, seen)
+
+    def launch(self):
+        """`ResidentEvalLoader._launch` on the static buffers -> the batch dict (event lists of `capacity` rows)."""
+        return self.loader._launch(self.table_dev, self.capacity, *self.buffers)

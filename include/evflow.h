@@ -731,6 +731,29 @@ int evf_zero_segments_if(const int* flag, void* const* dst, const int64_t* bytes
  * offset[k] + n[k] > row_floats. */
 int evf_store_segments_at(const int64_t* row, int64_t nrows, float* log, int64_t row_floats, const void* const* src,
                           const int* offset, const int* n, int nseg, void* stream);
+/* evf_aee_at (csrc/evf_eval_log.hip): the AEE of ONE pass of a replayed evaluation (evaluate.ResidentAEEStep) -- the reference's
+ * AEE.forward (reference loss/flow.py:582-628) on the pass' own flow, event mask and ground-truth map, as the evaluation
+ * loop calls it once per ground-truth interval (reference eval_flow.py:169-176) -- reduced on the device and stored into a
+ * row of a device log.  flow, gt [B,2,H,W], mask [B,H,W] float32; dt_gt, dt_input: DEVICE double [B], per sample
+ * ratio = (float)dt_gt[b] / (float)dt_input[b], one IEEE division without a guard (dt_input = 0 gives inf / nan like the float32
+ * torch division of loss.flow.AEE.forward); the per-pixel arithmetic is evf_aee's, operation for operation.
+ * Launch 1, grid (S, B), S = evf_aee_at_stripes(H, W) = ceil(H W / 2048): block (s, b) reduces its stripe of 2048 pixels (256
+ * threads, a strided loop per thread, evf_block_sum's butterflies) and stores (sum err, n valid, n outliers) to ws[b][s][3];
+ * 16-byte loads when W % 4 == 0 and flow, gt and mask are 16-byte aligned, dword loads otherwise.  Launch 2, one block: the S
+ * partials of every sample added in stripe order, aee_b = se / (nv + 1e-9f), percent_b = (sum over the WHOLE batch of the
+ * outlier counts) / (nv_b + 1e-9f) (the quirk of loss/flow.py:626), the two batch means as sequential float32 sums over
+ * b = 0 .. B - 1 divided by B, and [aee_0 .. aee_{B-1}, mean, percent_0 .. percent_{B-1}, mean] stored at
+ * log[row[0] * row_floats + offset ..].  row: ONE int64 word in device memory; outside 0 .. nrows - 1 nothing is stored.
+ * ws: at least B * S * 3 floats (ws_floats its size), need not be zero; after a call that stored its row, ws[b][0][0..2] holds
+ * sample b's (sum err, n valid, n outliers) and ws[b][s], s > 0, stripe s's partials.  Two plain launches
+ * on one stream, no atomics, no ticket: the same bits from call to call; allocates nothing, copies nothing, can be captured.
+ * EVF_EINVAL, before any launch: a null pointer, a non-positive B, H, W, nrows or row_floats, B or S > 65535, a negative
+ * offset, offset + 2 (B + 1) > row_floats, ws_floats < B * S * 3, a log, ws, flow, gt or mask that is not 4-byte aligned,
+ * dt_gt, dt_input or row not 8-byte aligned.  evf_aee_at_stripes: S, or EVF_EINVAL for non-positive sizes / H W >= 2^31 - 2048. */
+int evf_aee_at_stripes(int H, int W);
+int evf_aee_at(const float* flow, const float* gt, const float* mask, const double* dt_gt, const double* dt_input, int B, int H,
+               int W, float flow_scaling, const int64_t* row, int64_t nrows, float* log, int64_t row_floats, int offset,
+               float* ws, int64_t ws_floats, void* stream);
 
 /* ------------------------------------------------------------------ device-resident evaluation
  * (dataloader/resident_eval.py, csrc/evf_resident_eval.hip): data.mode time / frames / gtflow_dt1 / gtflow_dt4 on the arena
