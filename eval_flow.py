@@ -6,6 +6,8 @@ No MLflow / visualiser; results are printed as JSON.
   python eval_flow.py --config configs/eval_flow.yml --train-config configs/train_SNN.yml --synthetic [--weights model.pth]
   python eval_flow.py ... --resident --graphed [--per-sequence]   # data.mode events: a graph launch per evaluated window;
                                                                   # gtflow_dt1 / gtflow_dt4 with metrics [AEE]: one per pass
+  python eval_flow.py ... --store DIR [--render device]           # PNGs in the reference's folder layout; device: every image of
+                                                                  # a pass and every slot of the batch from one evf_render_sheet launch
 """
 
 import argparse
@@ -21,6 +23,40 @@ from event_flow_amd.loss import flow as metrics_mod
 from event_flow_amd.models.model import MODELS
 from event_flow_amd.utils.iwe import compute_pol_iwe
 from event_flow_amd.utils.utils import load_model
+
+
+def render_refusal(args, device):
+    """Why --render does not serve these arguments (None: it does).  Host-only: asked before any device work."""
+    render = getattr(args, "render", "host")
+    if render == "host":
+        return None
+    if render != "device":
+        return f"--render {render}: host or device"
+    if not getattr(args, "store", ""):
+        return "--render device colour-codes the STORED images on the GPU: add --store DIR, or drop --render device"
+    if torch.device(device).type != "cuda":
+        return (f"--render device runs evf_render_sheet on a CUDA device, and this evaluation runs on '{device}': use --render host "
+                "(the numpy renderer)")
+    return None
+
+
+def store_folders(data, synthetic, B):
+    """The folder of every batch slot for --store --render device: the stem of the file the slot reads now; the synthetic loader
+    reads none and is numbered like the host renderer's folders.
+    A slot that restarts takes sequence number max + 1 and opens files[number % len(files)], and the pass ends only after
+    len(files) restarts, so with two or more slots a file can be opened a second time before the pass is over, even while
+    another slot still reads it.  Every (slot, sequence number) is one visit with a folder of its own: the stem for a file's first
+    visit (number < len(files)), `<stem>_visit<k>` for visit k = number // len(files) after it.  The numbers of the slots differ,
+    so the names of a batch differ, never change while a slot stays on its sequence, and never come back.
+    Asks the loader's slot table while the batch is out: the loader must not read ahead (H5Loader(prefetch=0))."""
+    if synthetic:
+        seq = getattr(data, "seq_num", 0)
+        return ["seq%03d" % seq] if B == 1 else ["seq%03d_slot%d" % (seq, b) for b in range(B)]
+    names = []
+    for b, f in enumerate(slot_files(data)):
+        visit = data.batch_idx[b] // len(data.files)
+        names.append(f.split(".")[0] + ("_visit%d" % visit if visit else ""))
+    return names
 
 
 def test(args, config_parser, graphed_replay=True):
@@ -50,6 +86,9 @@ def test(args, config_parser, graphed_replay=True):
             raise _lib.EvflowError(why)
     if per_sequence and args.synthetic:
         raise _lib.EvflowError("--per-sequence reports per sequence FILE; the synthetic loader reads none: drop --synthetic")
+    why = render_refusal(args, device)
+    if why:
+        raise _lib.EvflowError(why)
     if torch.device(device).type == "cuda":
         torch.cuda.set_device(device)  # the evf_* launches go to the current device's stream (loader.gpu may not be 0)
 
@@ -89,14 +128,19 @@ def test(args, config_parser, graphed_replay=True):
     else:
         from event_flow_amd.dataloader.h5 import H5Loader
 
-        # (--per-sequence asks the loader which file a slot reads while its batch is out: no reader thread running ahead)
-        data = H5Loader(config, config["model"]["num_bins"], device=device, **({"prefetch": 0} if per_sequence else {}))
+        # (--per-sequence and --render device ask the loader which file a slot reads while its batch is out: no reader thread
+        # running ahead, which advances batch_idx before the batches of the old sequence have been consumed)
+        ask_slots = per_sequence or (bool(args.store) and getattr(args, "render", "host") == "device")
+        data = H5Loader(config, config["model"]["num_bins"], device=device, **({"prefetch": 0} if ask_slots else {}))
 
     vis = None
-    if args.store:  # stored PNGs in the reference's folder layout (utils/visualization.py:120-226); batch size 1
+    render = getattr(args, "render", "host")
+    if args.store:  # stored PNGs in the reference's folder layout (utils/visualization.py:120-226); --render host: batch size 1
         from event_flow_amd.utils.visualization import Visualization
 
-        vis = Visualization(config, eval_id=0, path_results=args.store.rstrip("/") + "/")
+        vis = Visualization(config, eval_id=0, path_results=args.store.rstrip("/") + "/", render=render)
+    # the three window images (reference eval_flow.py:201-210): events mode, input windows shorter than the evaluated one
+    window_images = vis is not None and config["data"]["mode"] == "events" and config["data"]["window"] < config["data"]["window_eval"]
     if graphed and config["data"]["mode"] != "events":  # (graphed_refusal: AEE alone on ground-truth windows)
         return _test_graphed_aee(config, model, data, per_sequence, graphed_replay)
     if graphed:
@@ -118,9 +162,10 @@ def test(args, config_parser, graphed_replay=True):
                                   inputs["event_list_pol_mask"][:, :, 0:1], inputs["event_list_pol_mask"][:, :, 1:2],
                                   flow_scaling=config["metrics"]["flow_scaling"], round_idx=True)
             iwe_sharpness.append(iwe.sum(1).var(dim=(1, 2)).mean())
-            if vis is not None and iwe.shape[0] == 1:
+            storing = vis is not None and (render == "device" or iwe.shape[0] == 1)
+            if storing:
                 flow_vis = x["flow"][-1] * inputs["event_mask"] if config["model"].get("mask_output", True) else x["flow"][-1]
-                vis.store(inputs, flow_vis, iwe, "seq%03d" % getattr(data, "seq_num", 0), ts=getattr(data, "last_proc_timestamp", None))
+            window_vis = (None, None, None)
             for metric in criteria:
                 metric.event_flow_association(x["flow"], inputs)
             for i, name in enumerate(names):
@@ -152,7 +197,13 @@ def test(args, config_parser, graphed_replay=True):
                             per_seq.add("AEE_percent_outliers", files, val[1].reshape(-1).tolist())
                         else:
                             per_seq.add(name, files, val.reshape(-1).tolist())
+                    if i == 0 and storing and window_images:  # the first metric's window, before its reset
+                        window_vis = (criteria[i].compute_window_events(), criteria[i].compute_masked_window_flow(),
+                                      criteria[i].compute_window_iwe())
                     criteria[i].reset()
+            if storing:  # (after the metrics, as in the reference: eval_flow.py:221-232)
+                sequence = store_folders(data, args.synthetic, iwe.shape[0]) if render == "device" else "seq%03d" % getattr(data, "seq_num", 0)
+                vis.store(inputs, flow_vis, iwe, sequence, *window_vis, ts=getattr(data, "last_proc_timestamp", None))
     out = {"model": config["model"]["name"], "iwe_variance": float(torch.stack(iwe_sharpness).mean())}
     for name, r in results.items():
         out[name] = r["metric"] / max(r["it"], 1)
@@ -219,6 +270,12 @@ if __name__ == "__main__":
                              "[AEE]: every PASS is one job-table copy plus one hipGraph launch, AEE reduced on the device")
     parser.add_argument("--per-sequence", action="store_true", dest="per_sequence",
                         help="also report every metric per sequence file (\"per_sequence\": {file: {metric: mean, \"it\": n}})")
-    parser.add_argument("--store", default="", help="directory that receives results/eval_0/<sequence>/{events,flow,iwe,...}/*.png")
+    parser.add_argument("--store", default="", help="directory that receives results/eval_0/<sequence>/{events,flow,iwe,...}/*.png; "
+                                                    "in data.mode events with window < window_eval also events_window, flow_window and "
+                                                    "iwe_window, at every pass whose first metric fired")
+    parser.add_argument("--render", choices=["host", "device"], default="host",
+                        help="with --store: host colour-codes every image in numpy (batch size 1, one sequence slot); device "
+                             "colour-codes every image of a pass and every slot of the batch in one evf_render_sheet launch and one "
+                             "copy, slot b under the stem of the file it reads (needs --store and a CUDA device)")
     args = parser.parse_args()
     test(args, YAMLParser(args.config))

@@ -62,6 +62,8 @@ SIGNATURES = {
     # device row word, nrows, log, row_floats, offset, ws, ws_floats  /  the stripes per sample that size ws (B * S * 3 floats)
     "evf_aee_at": [P, P, P, P, P, I, I, I, F, P, L, P, L, I, P, L, P],
     "evf_aee_at_stripes": [I, I],
+    # stored visualisations as one uint8 frame sheet: host arrays src / kind, nimg, B, H, W, scheme, k_lo, g_lo, k_hi, g_hi, out
+    "evf_render_sheet": [P, P, I, I, I, I, I, I, ctypes.c_double, I, ctypes.c_double, P, P],
     # device-resident evaluation (dataloader/resident_eval.py): ts, total, seg_begin, seg_len, query, Q, out
     "evf_ts_search": [P, L, P, P, P, L, P, P],
     # arena columns, total, first, count, flags, J, Npad, H, W, ev, dt_input

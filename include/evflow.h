@@ -755,6 +755,37 @@ int evf_aee_at(const float* flow, const float* gt, const float* mask, const doub
                int W, float flow_scaling, const int64_t* row, int64_t nrows, float* log, int64_t row_floats, int offset,
                float* ws, int64_t ws_floats, void* stream);
 
+/* evf_render_sheet (csrc/evf_render.hip): the stored visualisations of one pass (utils/visualization.py,
+ * Visualization(render="device")) colour-coded on the device into one frame sheet out [B][nimg][H][W][3] uint8, PNG channel order
+ * R, G, B, in ONE launch.  src / kind: HOST arrays of nimg <= 8 entries, passed by value in the launch's arguments (the
+ * evf_add_segments convention), so the call allocates nothing, copies nothing and can be captured.  Image k of sample b is
+ * read from src[k] (device memory, [B,2,H,W]) and written to out[b][k]:
+ *   EVF_RENDER_COUNTS  float32 per-polarity counts (channel 0 positive, 1 negative): events_to_image(...) * 255 -> rint -> clip to
+ *                      0..255.  Per channel the 1st and the 99th percentile of its H W values as numpy's percentile(method =
+ *                      "linear") forms them: order statistics k and min(k + 1, n - 1) -- EXACT for arbitrary finite floats, ties
+ *                      included (a radix select on order-preserving keys with LDS histograms) -- and numpy's lerp in float64,
+ *                      a + (b - a) g, or b - (b - a) (1 - g) from g = 0.5 on.  k_lo / g_lo and k_hi / g_hi are the positions of
+ *                      the two percentiles, computed by the CALLER in numpy's own arithmetic (utils.visualization.
+ *                      percentile_position): q = p / 100, vi = (n - 1) q, k = floor(vi), g = vi - k, in float64.
+ *                      top = max(p99(pos), p99(neg)), lo = p1(channel); value = clip((x - lo) / (top - lo), 0, 1), or clip(x, 0, 1)
+ *                      when lo == top, all float64.  scheme 0 (green_red): R = negative, G = positive, B = 0; scheme 1 (gray):
+ *                      0.5 + 0.5 pos - 0.5 neg in all three channels.  Byte-equal to the host renderer.
+ *   EVF_RENDER_FLOW    float32 flow (channel 0 x, 1 y): flow_to_image in float64 from the float32 components -- mag = hypot(x, y),
+ *                      val = (mag - min) / span over the image (mag - min when span == 0), hue = (atan2(y, x) + pi) / (2 pi),
+ *                      HSV -> RGB with s = 1, 255 c truncated toward zero.
+ *   EVF_RENDER_FRAME   uint8 frames: channel 1 copied into R = G = B.
+ * One block of 1024 threads per (sample, image) makes strided passes over its image; no block cooperates with another, no
+ * atomics on global memory, no workspace: the same bits from call to call.  No FMA contraction in the colour arithmetic.
+ * A NaN input may give any colour; no index depends on the values beyond (key >> shift) & 255.
+ * EVF_EINVAL, before any launch: src, kind, out or a src[k] NULL, nimg outside 1..8, an unknown kind or scheme, a non-positive
+ * B, H or W, H W > 2^18, B nimg > 65535, k_lo or k_hi outside 0 .. H W - 1, g_lo or g_hi outside [0, 1) or NaN, a float source
+ * that is not 4-byte aligned. */
+#define EVF_RENDER_COUNTS 0
+#define EVF_RENDER_FLOW 1
+#define EVF_RENDER_FRAME 2
+int evf_render_sheet(const void* const* src, const int* kind, int nimg, int B, int H, int W, int scheme, int k_lo, double g_lo,
+                     int k_hi, double g_hi, uint8_t* out, void* stream);
+
 /* ------------------------------------------------------------------ device-resident evaluation
  * (dataloader/resident_eval.py, csrc/evf_resident_eval.hip): data.mode time / frames / gtflow_dt1 / gtflow_dt4 on the arena
  * above.  Every entry: EVF_EINVAL for a null pointer, a non-positive size or a grid beyond the launch limits.
