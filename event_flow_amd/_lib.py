@@ -62,6 +62,17 @@ SIGNATURES = {
     # device row word, nrows, log, row_floats, offset, ws, ws_floats  /  the stripes per sample that size ws (B * S * 3 floats)
     "evf_aee_at": [P, P, P, P, P, I, I, I, F, P, L, P, L, I, P, L, P],
     "evf_aee_at_stripes": [I, I],
+    # training log (monitor.TrainMonitor).  grad, device seg_off / seg_n, nseg, max_n, ws, ws_floats  /  ws, ws_floats, device
+    # seg_n, nseg, max_n, norm_ws, max_norm, device loss (or NULL), device row word, nrows, log, row_floats, offset
+    "evf_grad_stats_chunk": [],
+    "evf_grad_stats_ws": [I, L],
+    "evf_grad_stats_partial": [P, P, P, I, L, P, L, P],
+    "evf_grad_stats_store": [P, L, P, I, L, P, F, P, P, L, P, L, I, P],
+    # host array src, nsrc, n_words, ws, slot0, ws_slots  /  ws, ws_slots, host array slot_layer, nslots, nlayers, total bits per
+    # layer, device row word, nrows, log, row_floats, offset
+    "evf_spike_count_parts": [],
+    "evf_spike_count": [P, I, L, P, I, I, P],
+    "evf_spike_rates_store": [P, I, P, I, I, L, P, L, P, L, I, P],
     # stored visualisations as one uint8 frame sheet: host arrays src / kind, nimg, B, H, W, scheme, k_lo, g_lo, k_hi, g_hi, out
     "evf_render_sheet": [P, P, I, I, I, I, I, I, ctypes.c_double, I, ctypes.c_double, P, P],
     # device-resident evaluation (dataloader/resident_eval.py): ts, total, seg_begin, seg_len, query, Q, out
@@ -233,7 +244,7 @@ NETWORK_SIGNATURES = {
 RESTYPES = {"evf_head1x1_ws": ctypes.c_int64, "evf_comm_last_error": ctypes.c_char_p, "evf_conv2d_packed_size": ctypes.c_int64, "evf_conv2d_b3_packed_size": ctypes.c_int64, "evf_conv2d_b3_ws": ctypes.c_int64, "evf_conv2d_wgrad_ws": ctypes.c_int64, "evf_cm_loss_ws": ctypes.c_int64, "evf_cm_loss_ws_det": ctypes.c_int64, "evf_cm_loss_bwd_ws_det": ctypes.c_int64,
             "evf_neuron_bwd_det_ws": ctypes.c_int64, "evf_clip_adam_det_ws": ctypes.c_int64,
             "evf_chan_reduce_det_ws": ctypes.c_int64, "evf_leaky_bwd_det_ws": ctypes.c_int64, "evf_conv2d_wgrad_det_ws": ctypes.c_int64,
-            "evf_norm_nonzero_det_ws": ctypes.c_int64}
+            "evf_norm_nonzero_det_ws": ctypes.c_int64, "evf_grad_stats_ws": ctypes.c_int64}
 SIGNATURES.update(NETWORK_SIGNATURES)
 
 _lib = None

@@ -247,6 +247,7 @@ class FireNetEngine:
         self.static_states = False
         self._final_target = None  # state tensors the last pass of the window writes into (model.final_states_into)
         self._final_hint = False
+        self._spike_taps = None  # a list while a monitor.TrainMonitor is attached: (layer, spike words) of every recorded pass
         self._static = [None] * len(cells)
         self._win = None
         self._packed = {}
@@ -627,6 +628,8 @@ class FireNetEngine:
                               1 if c.hard_reset else 0, _lib.ptr(v_out), _lib.ptr(z_out), _lib.ptr(zT_out))
             if record:
                 layers.append((in_bits, v_prev, z_prev, v_out, z_out, in_bitsT, zT_prev, pt_prev, pt_out, P_out))
+                if self._spike_taps is not None:  # (the open window's spike words, counted after the forward flush)
+                    self._spike_taps.append((i, z_out))
             in_bits, in_bitsT = z_out, zT_out
             new_states.append((v_out, z_out, zT_out, pt_out) if plif else (v_out, z_out, zT_out))
         if flow is None:

@@ -152,10 +152,14 @@ def _unit_gradient(loss):
     return _UNIT[key]
 
 
-def window_backward(model, loss_function, optimizer, passes, dp=None):
+def window_backward(model, loss_function, optimizer, passes, dp=None, monitor=None):
     """First half of a window: the passes, the loss and its backward (train_flow.py:129-154).
     Leaves this rank's gradient in the optimizer's flat buffer and, with `dp`, the
-    local loss in the buffer's tail, ready for the all-reduce."""
+    local loss in the buffer's tail, ready for the all-reduce.  `monitor` (monitor.TrainMonitor): the window's spike words are
+    counted between the forward flush and the backward."""
+    if monitor is not None:
+        _monitor_check(monitor, dp)
+        monitor.begin_window()
     defer = DEFER_FORWARD and hasattr(model, "defer_forward")
     if defer:
         model.defer_forward(True)  # fused FireNets: the window's hidden cells run diagonal by diagonal (engine.defer_forward)
@@ -168,6 +172,8 @@ def window_backward(model, loss_function, optimizer, passes, dp=None):
     finally:
         if defer:
             model.defer_forward(False)  # (launches what was recorded)
+    if monitor is not None:
+        monitor.count_spikes()
     if loss_function.overwrite_intermediate:
         loss_function.overwrite_intermediate_flow(x["flow"])
     loss = loss_function()
@@ -210,13 +216,26 @@ def window_forward_loss(model, loss_function, passes):
     return loss
 
 
-def window_apply(model, loss_function, optimizer, loss, dp=None):
+def _monitor_check(monitor, dp):
+    if dp is not None and dp.active:
+        raise _lib.EvflowError("a TrainMonitor logs one rank's step: logging under data parallelism is not supported; train on one "
+                               "rank, or pass monitor=None")
+
+
+def window_apply(model, loss_function, optimizer, loss, dp=None, monitor=None):
     """Second half: clip + Adam on the (reduced) gradient, state detach, loss reset
-    (train_flow.py:157-171).  Returns the 0-d (global) loss tensor."""
+    (train_flow.py:157-171).  Returns the 0-d (global) loss tensor.  `monitor`: the gradient's statistics are reduced BEFORE the
+    step, which clears the gradient, and the row is stored AFTER it, from the norm the step kernel left -- the logged norm and
+    clip coefficient are the applied ones."""
     staged = dp is not None and dp.active
     if staged:
         loss, _ = dp.staged(optimizer.comm)
+    if monitor is not None:
+        _monitor_check(monitor, dp)
+        monitor.before_step()
     optimizer.step()
+    if monitor is not None:
+        monitor.after_step(loss)
     optimizer.zero_grad()
     model.detach_states()
     loss_function.reset()
@@ -225,16 +244,16 @@ def window_apply(model, loss_function, optimizer, loss, dp=None):
     return loss.detach().clone() if staged else loss.detach()
 
 
-def train_window(model, loss_function, optimizer, passes, dp=None):
+def train_window(model, loss_function, optimizer, passes, dp=None, monitor=None):
     """One truncated-BPTT window = one optimizer step (train_flow.py:129-171).
     `passes`: list of dicts with event_cnt, event_voxel, event_list,
     event_list_pol_mask, event_mask (GPU tensors).  Returns the 0-d loss tensor
     (no host sync).  With `dp` the flat gradient (+ loss) is SUM all-reduced over
     the ranks between the two halves (the loss sums over the batch)."""
-    loss = window_backward(model, loss_function, optimizer, passes, dp)
+    loss = window_backward(model, loss_function, optimizer, passes, dp, monitor)
     if dp is not None:
         dp.reduce(optimizer.comm)
-    return window_apply(model, loss_function, optimizer, loss, dp)
+    return window_apply(model, loss_function, optimizer, loss, dp, monitor)
 
 
 class StreamReplicas:
@@ -505,13 +524,22 @@ class ResidentWindowStep(GraphedWindowStep):
         loss, info = stepper.step()      # 0-d loss tensor (no host sync); info: reset, n_discarded, done
     """
 
-    def __init__(self, model, loss_function, optimizer, loader, P, warmup=2, replay=True):
+    def __init__(self, model, loss_function, optimizer, loader, P, warmup=2, replay=True, monitor=None):
         for name in ("plan_window", "_job_table", "_launch_cut"):
             if not hasattr(loader, name):
                 raise _lib.EvflowError("ResidentWindowStep needs a ResidentLoader (the windows are cut out of its device-resident arena)")
         super().__init__(model, loss_function, optimizer, loader.num_bins, loader.res, dp=None, warmup=warmup)
         self.loader, self.P, self.replay = loader, int(P), bool(replay)
-        self.window = ResidentWindow(loader, self.P)
+        # with a monitor (monitor.TrainMonitor) ONE int64 word behind the job table names the row of its log this step fills: the
+        # warm-up steps, replay=False and the two replayed graphs all log through the same launches
+        self.monitor = monitor
+        if monitor is not None:
+            if monitor.steps != 0:
+                raise _lib.EvflowError("ResidentWindowStep: a TrainMonitor that has logged steps already (step k goes to row k % rows)")
+            self.window = ResidentWindow(loader, self.P, extra_words=1)
+            monitor.use_row_word(self.window.table_dev.data_ptr() + 8 * self.window.base)
+        else:
+            self.window = ResidentWindow(loader, self.P)
         # ResidentLoader._job_table: first | flags, slot reset | window reset
         self._reset_flag = self.window.table_dev.data_ptr() + 16 * loader.batch_size * self.P
         self.passes = None  # the window buffers of the last step (views of static tensors once the graphs replay)
@@ -532,7 +560,7 @@ class ResidentWindowStep(GraphedWindowStep):
                 # (the loop's `model.reset_states()`: the state THIS graph reads, cleared under the table's reset word)
                 zero_states_if(self._reset_flag, self.model.state_buffers())
                 passes = self.window.launch()
-                loss = train_window(self.model, self.lossf, self.opt, passes)
+                loss = train_window(self.model, self.lossf, self.opt, passes, monitor=self.monitor)
             self.graphs.append((g, loss, self.model.state_buffers(), passes))
 
     def step(self, plan=None):
@@ -546,13 +574,15 @@ class ResidentWindowStep(GraphedWindowStep):
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
             L.observe(discarded)
-            self.window.stage(group, self.seen)
+            extra = self.window.stage(group, self.seen)
+            if self.monitor is not None:
+                extra[0] = self.monitor.next_row()  # (= seen % rows; raises when that row was not drained)
             self.window.send()
             if not self.replay or self.seen < self.warmup:
                 if reset:
                     self.model.reset_states()
                 self.passes = self.window.launch()
-                loss = train_window(self.model, self.lossf, self.opt, self.passes)
+                loss = train_window(self.model, self.lossf, self.opt, self.passes, monitor=self.monitor)
                 self.stats["eager"] += 1
             else:
                 if self.graphs is None:
@@ -567,6 +597,8 @@ class ResidentWindowStep(GraphedWindowStep):
                 self.stats["replayed_discarded"] += 1 if discarded else 0
                 self.stats["graph_b" if gi else "graph_a"] += 1
             self.seen += 1
+            if self.monitor is not None:
+                self.monitor.advance()
         cur.wait_stream(self.stream)
         self.stats["discarded"] += len(discarded)
         L.new_seq, L.pass_done = reset, group[-1][2]

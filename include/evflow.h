@@ -755,6 +755,57 @@ int evf_aee_at(const float* flow, const float* gt, const float* mask, const doub
                int W, float flow_scaling, const int64_t* row, int64_t nrows, float* log, int64_t row_floats, int offset,
                float* ws, int64_t ws_floats, void* stream);
 
+/* Training log (csrc/evf_train_log.hip, monitor.TrainMonitor): the reference's vis.store_grads (utils/gradients.py get_grads: mean,
+ * min and max of |grad| per weight tensor after clipping, train_flow.py:159-160) and the spike rate of every layer, stored into a
+ * row of a device log by plain launches on one stream -- the evf_aee_at conventions: row is ONE int64 word in DEVICE memory,
+ * read by the kernels, a word outside 0 .. nrows - 1 is a defined no-op on the log; no atomics, no ticket, the same bits from call
+ * to call; nothing is allocated or copied, so the calls can be captured.  Every violation below is EVF_EINVAL before any launch.
+ *
+ * evf_grad_stats_partial -- BEFORE the optimizer step (evf_clip_adam_* clear the gradient as they apply it).  grad: the flat
+ * float32 gradient; seg_off / seg_n: DEVICE int64 arrays of nseg entries (element offset and length of every segment; the zoo's
+ * networks have more than 32 weight tensors), max_n >= every seg_n[k] (a longer segment is read up to max_n).  Grid
+ * (ceil(max_n / chunk), nseg), chunk = evf_grad_stats_chunk() = 4096: block (c, k) reduces elements [c chunk, min((c + 1) chunk,
+ * n_k)) of segment k -- 16-byte loads behind a scalar peel to the first 16-byte boundary, a scalar tail -- to the float64 sum
+ * of |g|, min |g|, max |g| and the number of NaNs, and stores them to ws[k][c] (5 words; ws need not be zero); a block past its
+ * segment's end leaves at once.  ws_floats >= evf_grad_stats_ws(nseg, max_n) = nseg * ceil(max_n / chunk) * 5 (EVF_EINVAL for
+ * nseg or max_n < 1, nseg > 65535, more than 65535 chunks).  EVF_EINVAL: a null pointer, a short ws, grad or ws not 4-byte
+ * aligned, seg_off or seg_n not 8-byte aligned.
+ *
+ * evf_grad_stats_store -- AFTER the optimizer step.  One block per segment adds the segment's partials in chunk order; total =
+ * norm_ws[0], the squared gradient norm the step kernel left (all three evf_clip_adam_* write it), coef = max_norm > 0 ?
+ * fminf(1, max_norm / (sqrtf(total) + 1e-6f)) : 1 -- the step kernel's own expression, so the logged values are the applied ones
+ * bit for bit.  log[row[0] * row_floats + offset ..] = [loss[0], sqrtf(total), coef, then per segment mean, min, max] (3 + 3 nseg
+ * floats) with min = fl32(min |g| * coef), max = fl32(max |g| * coef) (bit-equal to (g * coef).abs().min() / .max(): rounding is
+ * monotone), mean = (float)((double)coef * S / n); a NaN anywhere in a segment makes its three numbers NaN, infinities follow
+ * IEEE.  loss: a DEVICE float, or NULL -> the field is left as it is.  EVF_EINVAL: a null ws, seg_n, norm_ws, row or log, a
+ * non-positive nseg, max_n, nrows or row_floats, a negative offset, offset + 3 + 3 nseg > row_floats, a short ws, ws, log,
+ * norm_ws or loss not 4-byte aligned, seg_n or row not 8-byte aligned. */
+int evf_grad_stats_chunk(void);
+int64_t evf_grad_stats_ws(int nseg, int64_t max_n);
+int evf_grad_stats_partial(const float* grad, const int64_t* seg_off, const int64_t* seg_n, int nseg, int64_t max_n, float* ws,
+                           int64_t ws_floats, void* stream);
+int evf_grad_stats_store(const float* ws, int64_t ws_floats, const int64_t* seg_n, int nseg, int64_t max_n, const float* norm_ws,
+                         float max_norm, const float* loss, const int64_t* row, int64_t nrows, float* log, int64_t row_floats,
+                         int offset, void* stream);
+/* evf_spike_count: the set bits of nsrc <= 32 int32 word tensors of n_words words each (the fused engine's spike words [B,H,W],
+ * 32 channel bits per pixel), counted exactly.  src: a HOST array passed by value in the launch's arguments (the evf_add_segments
+ * convention); every source is device memory, 4-byte aligned (16-byte loads behind a scalar peel, a scalar tail; n_words is any
+ * number in 1 .. 2^31 - 1).  ws: uint32 [ws_slots][evf_spike_count_parts() = 32]; block (p, k) stores its partial to
+ * ws[slot0 + k][p], every partial is written, ws need not be zero.  EVF_EINVAL: src or ws NULL, nsrc outside 1..32, n_words
+ * outside 1 .. 2^31 - 1, slot0 < 0 or slot0 + nsrc > ws_slots, ws not 4-byte aligned, a NULL or misaligned source.
+ *
+ * evf_spike_rates_store: log[row[0] * row_floats + offset + l] = (float)((double)count_l / (double)total_bits_per_layer) for
+ * l < nlayers, count_l the int64 sum, in slot order, of the partials of the slots s < nslots with slot_layer[s] == l
+ * (slot_layer: a HOST int array of nslots <= 256 entries in 0 .. nlayers - 1, passed by value).  Exact arithmetic on an exact
+ * count and one rounding: a float32 row cannot hold the count itself.  EVF_EINVAL: a null pointer, nslots or nlayers outside
+ * 1..256, ws_slots < nslots, a slot_layer entry outside 0 .. nlayers - 1, a non-positive total, nrows or row_floats, a negative
+ * offset, offset + nlayers > row_floats, ws or log not 4-byte aligned, row not 8-byte aligned. */
+int evf_spike_count_parts(void);
+int evf_spike_count(const void* const* src, int nsrc, int64_t n_words, void* ws, int slot0, int ws_slots, void* stream);
+int evf_spike_rates_store(const void* ws, int ws_slots, const int* slot_layer, int nslots, int nlayers,
+                          int64_t total_bits_per_layer, const int64_t* row, int64_t nrows, float* log, int64_t row_floats,
+                          int offset, void* stream);
+
 /* evf_render_sheet (csrc/evf_render.hip): the stored visualisations of one pass (utils/visualization.py,
  * Visualization(render="device")) colour-coded on the device into one frame sheet out [B][nimg][H][W][3] uint8, PNG channel order
  * R, G, B, in ONE launch.  src / kind: HOST arrays of nimg <= 8 entries, passed by value in the launch's arguments (the

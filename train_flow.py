@@ -7,7 +7,10 @@ go to stdout and `--out` receives the checkpoint).  Data: the sequence files und
 the `.npz` flavour of the same layout, event_flow_amd/dataloader/h5.py), or `--synthetic` windows (moving dots with
 known motion).  `--fused-optimizer` swaps `clip_grad_norm_` + `torch.optim.Adam` for the fused flat-buffer kernel
 (same update rule).  `--resident --graphed --fused-optimizer` replays every optimizer step from a hipGraph that begins at the
-cut out of the device-resident sequences (event_flow_amd.train.ResidentWindowStep).
+cut out of the device-resident sequences (event_flow_amd.train.ResidentWindowStep).  `vis.store_grads: True` (the reference's
+key) or `--monitor DIR` log every optimizer step: `DIR/grads_w.csv` (mean, min, max of |grad| per weight tensor after clipping, the
+reference's layout) and, with `--fused-optimizer`, `DIR/train_log.csv` (loss, gradient norm, clip coefficient, spike rate per
+layer), collected on the device without a host read per step (event_flow_amd.monitor.TrainMonitor).
 
   python train_flow.py --config configs/train_SNN.yml --synthetic [--epochs 5] [--out model.pth]
 """
@@ -22,6 +25,7 @@ import torch
 from event_flow_amd.configs.parser import YAMLParser
 from event_flow_amd.loss.flow import EventWarping
 from event_flow_amd.models.model import MODELS
+from event_flow_amd import monitor as monitoring
 from event_flow_amd.parallel import DataParallel
 from event_flow_amd.train import FlatAdam
 from event_flow_amd.utils.utils import load_model
@@ -41,14 +45,25 @@ def _graphed_refusal(args):
     return None
 
 
-def train_graphed(args, config, model, loss_function, optimizer, data, n_epochs, replay=True):
+MONITOR_ROWS = 1024  # rows of the monitor's device log: drained at every epoch end and whenever the ring is about to wrap
+
+
+def _monitor_dir(args, config):
+    """Where the step logs go (None: no monitor): --monitor DIR, or with vis.store_grads the directory of --out, or "."."""
+    directory = getattr(args, "monitor", None)
+    if directory is None and config["vis"].get("store_grads", False):
+        directory = os.path.dirname(args.out) if args.out else "."
+    return (directory or ".") if directory is not None else None
+
+
+def train_graphed(args, config, model, loss_function, optimizer, data, n_epochs, replay=True, monitor=None, csvlog=None):
     """The epochs of `train` with every optimizer step taken by a ResidentWindowStep: the same steps on the same batches as the
     loop below (ResidentPlan.plan_steps), per-epoch losses and the best-loss checkpoint by the same arithmetic, closed when the
     first step of a later epoch arrives and after the last step.  -> (history, best loss, the stepper's counters)."""
     from event_flow_amd.train import ResidentWindowStep
 
     P = -(-int(config["data"]["window_loss"]) // int(config["data"]["window"]))  # passes until window_loss events are collected
-    stepper = ResidentWindowStep(model, loss_function, optimizer, data, P, replay=replay)
+    stepper = ResidentWindowStep(model, loss_function, optimizer, data, P, replay=replay, monitor=monitor)
     device = data.device
     best_loss, history = 1.0e6, []
     t_start = time.time()
@@ -57,6 +72,8 @@ def train_graphed(args, config, model, loss_function, optimizer, data, n_epochs,
     def close_epoch():
         nonlocal best_loss
         epoch_loss = float(state["loss"]) / max(state["samples"], 1)
+        if monitor is not None:  # (the epoch end synchronises already)
+            csvlog.write(len(history), monitor.drain())
         history.append(epoch_loss)
         if config["vis"].get("verbose", False):
             print("Train Epoch: {:04d}  Loss: {:.6f}  ({} optimizer steps, {:.1f} s)".format(len(history) - 1, epoch_loss,
@@ -70,6 +87,8 @@ def train_graphed(args, config, model, loss_function, optimizer, data, n_epochs,
     for discarded, group, reset, epoch in data.plan_steps(P, n_epochs):
         while len(history) < epoch:
             close_epoch()
+        if monitor is not None and monitor.full:  # the ring is about to wrap
+            csvlog.write(len(history), monitor.drain())
         loss, _info = stepper.step((discarded, group, reset))
         with torch.cuda.stream(stepper.stream):  # before the next replay rewrites the graph's loss tensor
             state["loss"] += loss
@@ -91,6 +110,11 @@ def train(args, config_parser, graphed_replay=True):
         print("Config error: Training pipeline not compatible with frames mode.")
         raise AttributeError
     config = config_parser.combine_entries(config)
+    monitor_dir = _monitor_dir(args, config)
+    if monitor_dir is not None:  # (refused on the host, before any device work)
+        why = monitoring.refusal(fused_optimizer=bool(args.fused_optimizer), want_rates=getattr(args, "monitor", None) is not None)
+        if why:
+            raise SystemExit(why)
     model = None
     if graphed:  # (built on the host first: the refusal comes before any device work)
         model = MODELS[config["model"]["name"]](config["model"].copy())
@@ -145,18 +169,28 @@ def train(args, config_parser, graphed_replay=True):
         dp.broadcast(optimizer.flat_param)
         optimizer.step_invalidate()
     optimizer.zero_grad()
+    monitor = csvlog = None
+    if monitor_dir is not None and args.fused_optimizer:
+        monitor = monitoring.TrainMonitor(model, optimizer, rows=MONITOR_ROWS)
+        csvlog = monitoring.CsvLog(monitor_dir, monitor.columns())
+    elif monitor_dir is not None:  # vis.store_grads beside torch's optimizer: read on the host after clip_grad_norm_
+        from event_flow_amd.utils.gradients import get_grads
+
+        csvlog = monitoring.CsvLog(monitor_dir, monitoring.grad_columns(model))
 
     n_epochs = args.epochs if args.epochs is not None else config["loader"]["n_epochs"]
     best_loss, history = 1.0e6, []
     t_start = time.time()
     data.shuffle()  # once, before the first epoch (train_flow.py:92)
     if graphed:
-        history, best_loss, counters = train_graphed(args, config, model, loss_function, optimizer, data, n_epochs, graphed_replay)
+        history, best_loss, counters = train_graphed(args, config, model, loss_function, optimizer, data, n_epochs, graphed_replay,
+                                                     monitor, csvlog)
         print(json.dumps({"model": config["model"]["name"], "epochs": n_epochs, "loss_per_epoch": history, "best_loss": best_loss,
                           "ranks": world, "graphed": counters}))
         return history
     for epoch in range(n_epochs):
         train_loss, samples, steps = torch.zeros((), device=device), 0, 0
+        host_grads = []  # vis.store_grads without the fused optimizer: one get_grads dict per step
         batches = iter(data)
         while True:
             inputs = next(batches, None)
@@ -170,6 +204,8 @@ def train(args, config_parser, graphed_replay=True):
                 loss_function.reset()
                 model.reset_states()
                 optimizer.zero_grad()
+                if monitor is not None:
+                    monitor.begin_window()  # (the spike words of the passes dropped here)
 
             x = model(inputs["event_voxel"], inputs["event_cnt"])
             loss_function.event_flow_association(x["flow"], inputs["event_list"], inputs["event_list_pol_mask"],
@@ -187,15 +223,25 @@ def train(args, config_parser, graphed_replay=True):
                 loss = loss_function()
                 samples += config["loader"]["batch_size"] * world
                 steps += 1
+                if monitor is not None:
+                    if monitor.full:  # the ring is about to wrap
+                        csvlog.write(epoch, monitor.drain())
+                    monitor.count_spikes()
                 loss.backward()
                 if dp:  # gradient (+ loss) summed over the ranks: the step below is the global-batch step
                     loss = dp.all_reduce_grads(optimizer.comm, loss)[0]
                 train_loss += loss.detach()  # no host sync inside the loop
                 if args.fused_optimizer:
+                    if monitor is not None:
+                        monitor.before_step()  # (the step clears the gradient)
                     optimizer.step()  # clip + Adam in one kernel
+                    if monitor is not None:
+                        monitor.after_step(loss)
                 else:
                     if clip is not None:
                         torch.nn.utils.clip_grad.clip_grad_norm_(model.parameters(), clip)
+                    if csvlog is not None:
+                        host_grads.append(get_grads(model.named_parameters()))
                     optimizer.step()
                 optimizer.zero_grad()
                 model.detach_states()
@@ -204,6 +250,10 @@ def train(args, config_parser, graphed_replay=True):
             batches.close()  # a rank that stops early (another rank ran out of files) ends its reader thread here
         epoch_loss = float(train_loss) / max(samples, 1)
         history.append(epoch_loss)
+        if monitor is not None:  # (the epoch end synchronises already)
+            csvlog.write(epoch, monitor.drain())
+        elif csvlog is not None and host_grads:
+            csvlog.write(epoch, [[g[c] for c in csvlog.grad_header[1:]] for g in host_grads])
         if config["vis"].get("verbose", False) and rank == 0:
             print("Train Epoch: {:04d}  Loss: {:.6f}  ({} optimizer steps, {:.1f} s)".format(epoch, epoch_loss, steps,
                                                                                              time.time() - t_start))
@@ -232,5 +282,8 @@ if __name__ == "__main__":
                         help="keep the sequence files in device memory and cut the input windows there (data.mode events)")
     parser.add_argument("--graphed", action="store_true",
                         help="with --resident --fused-optimizer: replay every optimizer step, from the cut to clip + Adam, from a hipGraph")
+    parser.add_argument("--monitor", default=None, metavar="DIR",
+                        help="log every optimizer step to DIR/grads_w.csv and DIR/train_log.csv (with --fused-optimizer: gradient "
+                             "statistics and spike rates collected on the device)")
     args = parser.parse_args()
     train(args, YAMLParser(args.config))
