@@ -8,15 +8,20 @@ No MLflow / visualiser; results are printed as JSON.
                                                                   # gtflow_dt1 / gtflow_dt4 with metrics [AEE]: one per pass
   python eval_flow.py ... --store DIR [--render device]           # PNGs in the reference's folder layout; device: every image of
                                                                   # a pass and every slot of the batch from one evf_render_sheet launch
+  python eval_flow.py ... --activity DIR                          # the reference's vis.activity: per pass the fraction of nonzero
+                                                                  # outputs of the nine FireNet layers, counted on the device by one
+                                                                  # launch per pass (every path above) -> DIR/activity.csv, "activity"
 """
 
 import argparse
 import json
+import sys
 
 import numpy as np
 import torch
 
 from event_flow_amd import _lib
+from event_flow_amd import activity as activity_mod
 from event_flow_amd.configs.parser import YAMLParser
 from event_flow_amd.evaluate import PerSequence, ResidentAEEStep, ResidentEvalStep, graphed_refusal, slot_files
 from event_flow_amd.loss import flow as metrics_mod
@@ -89,6 +94,7 @@ def test(args, config_parser, graphed_replay=True):
     why = render_refusal(args, device)
     if why:
         raise _lib.EvflowError(why)
+    activity_dir = getattr(args, "activity", "") or ("." if config.get("vis", {}).get("activity", False) else "")
     if torch.device(device).type == "cuda":
         torch.cuda.set_device(device)  # the evf_* launches go to the current device's stream (loader.gpu may not be 0)
 
@@ -110,6 +116,13 @@ def test(args, config_parser, graphed_replay=True):
     if args.weights:  # a state_dict file, a reference checkpoint (pickled model) or its MLflow run id under ./mlruns
         model = load_model(args.weights, model, device)
     model.eval()
+    activity_path = None
+    if activity_dir:  # asked on the host: the device log (fused FireNets), model(..., log=True) (general-path FireNets) or refused
+        activity_path = activity_mod.path(model)
+        if activity_path is None:
+            raise _lib.EvflowError(activity_mod.refusal(model))
+        if activity_path == "host":
+            print(activity_mod.refusal(model), file=sys.stderr)
 
     names = config.get("metrics", {}).get("name", [])
     criteria = [getattr(metrics_mod, m)(config, device, flow_scaling=config["metrics"]["flow_scaling"]) for m in names]
@@ -142,22 +155,50 @@ def test(args, config_parser, graphed_replay=True):
     # the three window images (reference eval_flow.py:201-210): events mode, input windows shorter than the evaluated one
     window_images = vis is not None and config["data"]["mode"] == "events" and config["data"]["window"] < config["data"]["window_eval"]
     if graphed and config["data"]["mode"] != "events":  # (graphed_refusal: AEE alone on ground-truth windows)
-        return _test_graphed_aee(config, model, data, per_sequence, graphed_replay)
+        return _test_graphed_aee(config, model, data, per_sequence, graphed_replay, activity_dir)
     if graphed:
-        return _test_graphed(config, model, criteria, names, data, per_sequence, graphed_replay)
+        return _test_graphed(config, model, criteria, names, data, per_sequence, graphed_replay, activity_dir)
     per_seq = PerSequence() if per_sequence else None
+    B = config["loader"]["batch_size"]
+    act_log = activity_mod.ActivityLog(model, B) if activity_path == "device" else None
+    act_report = activity_mod.Report(activity_dir, B, per_sequence) if activity_path else None
+    act_new, act_files, act_host = [], ([] if per_sequence else None), []
+
+    def drain_activity():
+        if act_log is not None:
+            batch, slots = act_log.fractions(act_log.drain())
+        else:  # the nine reads of every pass were made by model(..., log=True)
+            batch, slots = np.array(act_host, dtype=np.float64).reshape(-1, len(activity_mod.LAYERS)), None
+        act_report.add(batch, slots, act_new, act_files)
+        del act_new[:], act_host[:]
+        if act_files is not None:
+            del act_files[:]
+
     results = {m: {"metric": 0.0, "it": 0, **({"percent": 0.0} if m == "AEE" else {})} for m in names}
     iwe_sharpness = []
     idx_AEE = 0  # sub-windows since the last AEE evaluation (eval_flow.py:117,171-176)
     aee_every = 1 if args.synthetic else int(np.round(1.0 / config["data"]["window"]))
     with torch.no_grad():
         for inputs in data:
+            restarted = bool(data.new_seq)
             if data.new_seq:
                 data.new_seq = False
                 model.reset_states()
             if getattr(data, "pass_done", False):  # every sequence was visited (eval_flow.py:124-127)
                 break
-            x = model(inputs["event_voxel"], inputs["event_cnt"])
+            if activity_path == "host":
+                x = model(inputs["event_voxel"], inputs["event_cnt"], log=True)
+                act_host.append([x["activity"][layer] for layer in activity_mod.LAYERS])
+            else:
+                x = model(inputs["event_voxel"], inputs["event_cnt"])
+            if activity_path:
+                if act_log is not None:
+                    if act_log.full:
+                        drain_activity()
+                    act_log.record(*model.last_io())
+                act_new.append(restarted)
+                if act_files is not None:
+                    act_files.append(slot_files(data))
             iwe = compute_pol_iwe(x["flow"][-1], inputs["event_list"], config["loader"]["resolution"],
                                   inputs["event_list_pol_mask"][:, :, 0:1], inputs["event_list_pol_mask"][:, :, 1:2],
                                   flow_scaling=config["metrics"]["flow_scaling"], round_idx=True)
@@ -211,18 +252,32 @@ def test(args, config_parser, graphed_replay=True):
             out["AEE_percent_outliers"] = r["percent"] / max(r["it"], 1)
     if per_seq is not None:
         out["per_sequence"] = per_seq.summary()
+    if activity_path:
+        drain_activity()
+        act_report.into(out)
+        if act_log is not None:
+            act_log.close()
     print(json.dumps(out))
     return out
 
 
-def _test_graphed(config, model, criteria, names, data, per_sequence, replay):
+def _stepper_activity(model, B, passes, directory, per_sequence):
+    """The activity log of a replayed evaluation, sized for its passes (the host knows them: no ring), and its report."""
+    if not directory:
+        return None, None
+    return (activity_mod.ActivityLog(model, B, rows=max(passes, 1)), activity_mod.Report(directory, B, per_sequence))
+
+
+def _test_graphed(config, model, criteria, names, data, per_sequence, replay, activity_dir=""):
     """The loop above for `data.mode: events` on the resident loader, an evaluated window (P = ceil(window_eval / window)
     batches) per step: one table copy and one graph launch each, the results read once at the end (evaluate.py)."""
     P = -(-int(config["data"]["window_eval"]) // int(config["data"]["window"]))
     steps = list(data.plan_eval_steps(P))  # host-only: the number of evaluated windows sizes the result log
+    act_log, report = _stepper_activity(model, data.batch_size, sum(len(group) for group, _r, _t in steps), activity_dir, per_sequence)
     stepper = ResidentEvalStep(model, criteria, names, data, P, len(steps) - 1, config["metrics"]["flow_scaling"],
                                overwrite_intermediate=config["loss"].get("overwrite_intermediate", False), replay=replay,
-                               per_sequence=per_sequence)
+                               per_sequence=per_sequence, activity=act_log)
+    stepper.activity_report = report
     model.reset_states()
     for group, pass_reset, tail in steps:
         if tail:
@@ -234,15 +289,17 @@ def _test_graphed(config, model, criteria, names, data, per_sequence, replay):
     return out
 
 
-def _test_graphed_aee(config, model, data, per_sequence, replay):
+def _test_graphed_aee(config, model, data, per_sequence, replay, activity_dir=""):
     """The loop above for AEE alone in `data.mode` gtflow_dt1 / gtflow_dt4 on the resident loader, a PASS per step: one table
     copy and one graph launch each; which passes evaluate (the `idx_AEE` rule), how many there are and the width of the
     replayed buffers come from the host-only plan, the results are read once at the end (evaluate.ResidentAEEStep)."""
     plan = list(data.plan_eval_passes())
     capacity = max([job[2] for jobs, _restarted, _evaluate in plan for job in jobs] + [1])
     evaluations = sum(1 for _jobs, _restarted, evaluate in plan if evaluate)
+    act_log, report = _stepper_activity(model, data.batch_size, len(plan), activity_dir, per_sequence)
     stepper = ResidentAEEStep(model, data, len(plan), evaluations, capacity, config["metrics"]["flow_scaling"], replay=replay,
-                              per_sequence=per_sequence)
+                              per_sequence=per_sequence, activity=act_log)
+    stepper.activity_report = report
     model.reset_states()
     for jobs, restarted, evaluate in plan:
         stepper.step(jobs, restarted, evaluate)
@@ -270,6 +327,12 @@ if __name__ == "__main__":
                              "[AEE]: every PASS is one job-table copy plus one hipGraph launch, AEE reduced on the device")
     parser.add_argument("--per-sequence", action="store_true", dest="per_sequence",
                         help="also report every metric per sequence file (\"per_sequence\": {file: {metric: mean, \"it\": n}})")
+    parser.add_argument("--activity", default="", metavar="DIR",
+                        help="the reference's vis.activity (vis.activity: True in the configuration means --activity .): per pass "
+                             "the fraction of nonzero outputs of the nine FireNet layers, counted exactly on the device by one launch "
+                             "per pass -- inside the replayed graphs of --graphed as well -- and read once -> DIR/activity.csv and "
+                             "\"activity\" in the JSON (with --per-sequence per file, too); a general-path FireNet falls back to "
+                             "model(..., log=True) on the host")
     parser.add_argument("--store", default="", help="directory that receives results/eval_0/<sequence>/{events,flow,iwe,...}/*.png; "
                                                     "in data.mode events with window < window_eval also events_window, flow_window and "
                                                     "iwe_window, at every pass whose first metric fired")

@@ -73,6 +73,10 @@ SIGNATURES = {
     "evf_spike_count_parts": [],
     "evf_spike_count": [P, I, L, P, I, I, P],
     "evf_spike_rates_store": [P, I, P, I, I, L, P, L, P, L, I, P],
+    # activity log (activity.ActivityLog).  n_max  /  host arrays src, kind (int), n (int64), nsrc, B, device row word, row_mul,
+    # row_add, nrows, log (and the stream)
+    "evf_activity_parts": [L],
+    "evf_activity_at": [P, P, P, I, I, P, L, L, L, P, P],
     # stored visualisations as one uint8 frame sheet: host arrays src / kind, nimg, B, H, W, scheme, k_lo, g_lo, k_hi, g_hi, out
     "evf_render_sheet": [P, P, I, I, I, I, I, I, ctypes.c_double, I, ctypes.c_double, P, P],
     # device-resident evaluation (dataloader/resident_eval.py): ts, total, seg_begin, seg_len, query, Q, out

@@ -131,6 +131,33 @@ class _ReplayedSteps:
         self.graphs = None
         self.stats = {"eager": 0, "replayed": 0, "replayed_reset": 0, "graph_a": 0, "graph_b": 0}
 
+    def _init_activity(self, activity, per_sequence, passes):
+        """`activity`: an activity.ActivityLog (None: nothing changes) whose one launch follows every forward, inside the
+        captured graphs as well; the log is sized for the `passes` the host knows of (None: the caller vouches), not a ring."""
+        self.activity, self.activity_report = activity, None
+        self.pass_new = []  # per recorded pass: the loop reset the states in front of it
+        self.pass_files = [] if (activity is not None and per_sequence) else None  # ... and the file every slot reads
+        self._activity_out = None
+        if activity is None:
+            return
+        if activity.B != self.B or activity.model is not self.model:
+            raise _lib.EvflowError(f"{type(self).__name__}: the activity log serves another model or batch size")
+        if passes is not None and activity.rows < passes:
+            raise _lib.EvflowError(f"{type(self).__name__}: an activity log of {activity.rows} rows for {passes} passes")
+
+    def _activity_results(self, out, per_sequence):
+        """ "activity" (and "activity" under every file of "per_sequence") into `out`: the log's one host read."""
+        if self.activity is None:
+            return out
+        if self._activity_out is None:
+            from .activity import Report
+
+            report = self.activity_report if self.activity_report is not None else Report(None, self.B, per_sequence)
+            batch, slots = self.activity.fractions(self.activity.drain())
+            report.add(batch, slots, self.pass_new, self.pass_files)
+            self._activity_out = report
+        return self._activity_out.into(out)
+
     def _capture(self):
         home = self.model.state_buffers()
         if any(st is None for st in home):
@@ -187,6 +214,8 @@ class ResidentEvalStep(_ReplayedSteps):
     The first `warmup` steps, every step with `replay=False` and the tail (`step_tail`, fewer than P batches: forwarded and
     associated, never evaluated) run the same launches eagerly with `model.reset_states()` in place of the zero-fill.  No step
     reads a device value on the host; `results()` reads the log once.  The tail comes last: a replay does not follow it.
+    `activity`: an `activity.ActivityLog` of at least as many rows as the loop has passes -- its one launch follows every forward,
+    inside both graphs too (row = step row * P + p; the tail through the log's own word), and `results()` gains "activity".
 
         stepper = ResidentEvalStep(model, criteria, names, loader, P, rows, flow_scaling)
         for group, pass_reset, tail in loader.plan_eval_steps(P):
@@ -195,7 +224,7 @@ class ResidentEvalStep(_ReplayedSteps):
     """
 
     def __init__(self, model, criteria, names, loader, P, rows, flow_scaling, overwrite_intermediate=False, warmup=2,
-                 replay=True, per_sequence=False):
+                 replay=True, per_sequence=False, activity=None):
         for name in ("plan_eval_steps", "_job_table", "_launch_cut"):
             if not hasattr(loader, name):
                 raise _lib.EvflowError("ResidentEvalStep needs a ResidentLoader (the windows are cut out of its device-resident arena)")
@@ -214,12 +243,14 @@ class ResidentEvalStep(_ReplayedSteps):
         self.tail_sharp = []  # 0-d tensors of the tail passes
         self.row_files = [] if per_sequence else None
         self.stats["tail_passes"] = 0
+        self._init_activity(activity, per_sequence, self.rows * P)
 
     # ------------------------------------------------------------------ launches
-    def _passes(self, passes, pass_reset):
+    def _passes(self, passes, pass_reset, own_row=False):
         """Forward, image of warped events, sharpness scalar and association of every pass -> (sharpness scalars, last flow).
         `pass_reset` None: a captured graph, the state tensors the pass reads are zero-filled under its word of the table; else
-        the eager reset."""
+        the eager reset.  With an activity log: its launch behind every forward, into row (step row) * P + p, or (`own_row`, the
+        tail) into the row of the log's own word."""
         res = self.loader.res
         sharp, x = [], None
         for p, d in enumerate(passes):
@@ -231,6 +262,11 @@ class ResidentEvalStep(_ReplayedSteps):
             if p == self.P - 1:
                 self.model.mark_last_pass()
             x = self.model(d["event_voxel"], d["event_cnt"])
+            if self.activity is not None:
+                if own_row:
+                    self.activity.record(*self.model.last_io())
+                else:
+                    self.activity.record(*self.model.last_io(), row_word=self._row_word, row_mul=self.P, row_add=p)
             iwe = compute_pol_iwe(x["flow"][-1], d["event_list"], res, d["event_list_pol_mask"][:, :, 0:1],
                                   d["event_list_pol_mask"][:, :, 1:2], flow_scaling=self.flow_scaling, round_idx=True)
             sharp.append(iwe.sum(1).var(dim=(1, 2)).mean())
@@ -283,8 +319,18 @@ class ResidentEvalStep(_ReplayedSteps):
             self.window.send()
 
         self._step(send, list(pass_reset), any(pass_reset))
+        self._note_passes(group, pass_reset)
+        if self.activity is not None:
+            self.activity.advance(self.P)
         if self.row_files is not None:  # the file every slot reads in the window's last batch, where the loop evaluates
             self.row_files.append([os.path.basename(path) for path, _first, _flags, _restarted in group[-1][0]])
+
+    def _note_passes(self, group, pass_reset):
+        if self.activity is None:
+            return
+        self.pass_new += [bool(r) for r in pass_reset]
+        if self.pass_files is not None:
+            self.pass_files += [[os.path.basename(job[0]) for job in jobs] for jobs, _restarted, _done in group]
 
     def step_tail(self, group, pass_reset):
         """The fewer than P batches behind the last whole window: forwarded and associated like every batch, never evaluated
@@ -296,7 +342,8 @@ class ResidentEvalStep(_ReplayedSteps):
         cur = torch.cuda.current_stream()
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream), torch.no_grad():
-            sharp, _x = self._passes(self.loader.window_passes(group), list(pass_reset))
+            sharp, _x = self._passes(self.loader.window_passes(group), list(pass_reset), own_row=True)
+            self._note_passes(group, pass_reset)
             self.tail_sharp += sharp
             self.stats["tail_passes"] += len(group)
         cur.wait_stream(self.stream)
@@ -306,7 +353,7 @@ class ResidentEvalStep(_ReplayedSteps):
         torch.cuda.current_stream().wait_stream(self.stream)
         log = self.log[:self.seen]
         tail = torch.stack(self.tail_sharp) if self.tail_sharp else torch.empty(0, dtype=torch.float32, device=self.log.device)
-        return reduce_eval_log(log, tail, self.names, self.B, self.P, self.row_files)
+        return self._activity_results(reduce_eval_log(log, tail, self.names, self.B, self.P, self.row_files), self.row_files is not None)
 
 
 class ResidentAEEStep(_ReplayedSteps):
@@ -322,7 +369,8 @@ class ResidentAEEStep(_ReplayedSteps):
     `model.reset_states()`), the forward under no_grad, compute_pol_iwe, the sharpness scalar stored by
     evf_store_segments_at under the pass row, and evf_aee_at under the AEE row.  The first `warmup` passes and every pass with
     `replay=False` run the same launches eagerly with `model.reset_states()` in place of the zero-fill.  No step reads a
-    device value on the host; `results()` reads the two logs once.
+    device value on the host; `results()` reads the two logs once.  `activity`: an `activity.ActivityLog` of `passes` rows -- its
+    one launch follows the forward under the pass row, inside both graphs too, and `results()` gains "activity".
 
         plan = list(loader.plan_eval_passes())
         capacity = max([job[2] for jobs, _r, _e in plan for job in jobs] + [1])
@@ -332,7 +380,8 @@ class ResidentAEEStep(_ReplayedSteps):
         out = stepper.results()
     """
 
-    def __init__(self, model, loader, passes, evaluations, capacity, flow_scaling, warmup=2, replay=True, per_sequence=False):
+    def __init__(self, model, loader, passes, evaluations, capacity, flow_scaling, warmup=2, replay=True, per_sequence=False,
+                 activity=None):
         for name in ("plan_eval_passes", "_job_table", "_launch"):
             if not hasattr(loader, name):
                 raise _lib.EvflowError("ResidentAEEStep needs a ResidentEvalLoader (the windows are cut out of its device-resident "
@@ -358,6 +407,7 @@ class ResidentAEEStep(_ReplayedSteps):
         self.ws = torch.empty(self.B * stripes * 3, dtype=torch.float32, device=dev)
         self.evaluated = 0
         self.row_files = [] if per_sequence else None
+        self._init_activity(activity, per_sequence, self.passes)
 
     def _launches(self, reset):
         """The launches of one pass on the static buffers (see the class) -> what must stay allocated.  `reset` None: a
@@ -371,6 +421,8 @@ class ResidentAEEStep(_ReplayedSteps):
             self.model.reset_states()
         self.model.mark_last_pass()  # (every pass ends its graph: the next one starts from the state it leaves)
         x = self.model(d["event_voxel"], d["event_cnt"])
+        if self.activity is not None:  # (its launch: the pass row of the table names the log's row, too)
+            self.activity.record(*self.model.last_io(), row_word=self._pass_row)
         iwe = compute_pol_iwe(x["flow"][-1], d["event_list"], self.loader.res, d["event_list_pol_mask"][:, :, 0:1],
                               d["event_list_pol_mask"][:, :, 1:2], flow_scaling=self.flow_scaling, round_idx=True)
         sharp = iwe.sum(1).var(dim=(1, 2)).mean().to(torch.float32).view(1)
@@ -400,6 +452,11 @@ class ResidentAEEStep(_ReplayedSteps):
             self.window.send()
 
         self._step(send, bool(restarted), bool(restarted))
+        if self.activity is not None:
+            self.activity.advance()
+            self.pass_new.append(bool(restarted))
+            if self.pass_files is not None:
+                self.pass_files.append([os.path.basename(job[0]) for job in jobs])
         if evaluate:
             self.evaluated += 1
             if self.row_files is not None:  # the file every slot reads in the pass where the loop evaluates
@@ -423,4 +480,4 @@ class ResidentAEEStep(_ReplayedSteps):
             out[name] = total / max(it, 1)
         if per is not None:
             out["per_sequence"] = per.summary()
-        return out
+        return self._activity_results(out, per is not None)

@@ -210,6 +210,18 @@ class FireNet(BaseModel):
         if self._fused():
             self._eng().defer_backward(on)
 
+    def keep_io(self, on=True):
+        """While on, every fused forward pass keeps its input and its flow for last_io()."""
+        self._keep_io, self._last_io = bool(on), None
+
+    def last_io(self):
+        """(the input the last fused forward pass saw -- after norm_input --, the flow it returned), both detached: what
+        activity.ActivityLog counts beside the spike words of state_buffers().  Needs keep_io()."""
+        io = self.__dict__.get("_last_io")
+        if io is None:
+            raise RuntimeError("last_io(): no forward pass on the fused engine since keep_io()")
+        return io
+
     # -- state API (models/model.py:203-227) -------------------------------
     @property
     def states(self):
@@ -259,6 +271,8 @@ class FireNet(BaseModel):
 
         eng = self._eng()
         flow = eng.forward(x)
+        if self.__dict__.get("_keep_io"):  # (an activity.ActivityLog is attached)
+            self._last_io = (x.detach(), flow.detach())
 
         if log:  # fraction of non-zero outputs per layer, models/model.py:268-284
             eng.flush_forward()  # (recorded cells of this pass have not run yet: torch reads below would see stale memory)

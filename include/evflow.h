@@ -806,6 +806,33 @@ int evf_spike_rates_store(const void* ws, int ws_slots, const int* slot_layer, i
                           int64_t total_bits_per_layer, const int64_t* row, int64_t nrows, float* log, int64_t row_floats,
                           int offset, void* stream);
 
+/* evf_activity_at (csrc/evf_activity.hip): the spike activity of ONE evaluation pass (activity.ActivityLog) -- what the
+ * reference's model(..., log=True) reports, the nonzero outputs of every layer -- as exact integer counts per source and per
+ * sample, stored into a row of a device log by ONE plain launch: the evf_aee_at conventions.  src / kind / n: HOST arrays of
+ * nsrc entries in 1..16, passed by value in the launch's arguments (the evf_add_segments convention), so the call allocates
+ * nothing, copies nothing and can be captured.  Source k is device memory [B][n[k]], contiguous and 4-byte aligned (16-byte
+ * loads behind a scalar peel to the first 16-byte boundary, a scalar tail; n[k] is any number in 1 .. 2^27 - 1, so that 32 bits
+ * a word stay below 2^32 in one block):
+ *   EVF_ACT_FLOAT  the float32 elements with x != 0 as torch.ne(0) defines it, tested on the bits, (bits & 0x7fffffff) != 0:
+ *                  -0.0 is zero; NaN, +-inf and every denormal count, whatever the denormal mode.
+ *   EVF_ACT_WORDS  the set bits of int32 words (the fused engine's spike words [B,H,W], 32 channel bits per pixel).
+ * log: uint32 [nrows][nsrc][B][parts], parts = evf_activity_parts(max_k n[k]) (>= 1; EVF_EINVAL for n_max outside
+ * 1 .. 2^27 - 1).  Grid (parts, nsrc, B): block (p, k, b) counts elements [p s, min((p + 1) s, n[k])) of sample b of source k,
+ * s = ceil(n[k] / parts) rounded up to a multiple of 4, reduces them in the block (wave butterflies, then the four waves through
+ * LDS) and stores ONE word with a plain store; a block with an empty share stores 0, so EVERY word of the row is written and the
+ * log need not be cleared.  No atomics, no ticket, no workspace, no second launch: the same bits from call to call; the host
+ * adds the parts in int64.  The row is row[0] * row_mul + row_add (formed in 128 bits); row: ONE int64 word in DEVICE memory,
+ * read by the kernel; a result outside 0 .. nrows - 1 is a defined no-op (a row word of -1 skips).  row_mul / row_add let the P
+ * passes of one replayed window share the step's row word (row_mul = P, row_add = p).
+ * EVF_EINVAL, before any launch: a null pointer (src, kind, n, row, log or a src[k]), nsrc outside 1..16, an unknown kind, n[k]
+ * outside 1 .. 2^27 - 1, a non-positive B or nrows, B > 65535, a source or a log that is not 4-byte aligned, row not 8-byte
+ * aligned, a negative row_mul or row_add. */
+#define EVF_ACT_FLOAT 0
+#define EVF_ACT_WORDS 1
+int evf_activity_parts(int64_t n_max);
+int evf_activity_at(const void* const* src, const int* kind, const int64_t* n, int nsrc, int B, const int64_t* row,
+                    int64_t row_mul, int64_t row_add, int64_t nrows, uint32_t* log, void* stream);
+
 /* evf_render_sheet (csrc/evf_render.hip): the stored visualisations of one pass (utils/visualization.py,
  * Visualization(render="device")) colour-coded on the device into one frame sheet out [B][nimg][H][W][3] uint8, PNG channel order
  * R, G, B, in ONE launch.  src / kind: HOST arrays of nimg <= 8 entries, passed by value in the launch's arguments (the
