@@ -16,7 +16,6 @@ memory -- the log's own for eager passes, a word of a stepper's job table under 
 
 `ActivityCsv` appends drained passes to `activity.csv`.  Everything but `ActivityLog` runs on the host alone."""
 
-import csv
 import ctypes
 import os
 
@@ -24,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .devlog import DeviceLog, Ring, append_csv, on_fused_engine  # noqa: F401  (Ring: its users import it from here)
 
 LAYERS = ("0:input", "1:head", "2:G1", "3:R1a", "4:R1b", "5:G2", "6:R2a", "7:R2b", "8:pred")  # the names of model(..., log=True)
 ACT_FLOAT, ACT_WORDS = 0, 1  # EVF_ACT_FLOAT / EVF_ACT_WORDS (include/evflow.h)
@@ -66,10 +66,10 @@ def path(model):
     (`model(..., log=True)`: a FireNet on the general path) or None (refused).  Host only."""
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         return None
-    cp = getattr(model, "compute_path", None)
-    if cp is None:
+    fused, why = on_fused_engine(model)
+    if why is None:
         return None
-    return "device" if cp[0] == "fused" else "host"
+    return "device" if fused else "host"
 
 
 def refusal(model):
@@ -77,58 +77,20 @@ def refusal(model):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         return ("the activity log counts one rank's passes: logging under data parallelism (WORLD_SIZE > 1) is not supported; run "
                 "without torch.distributed.run (WORLD_SIZE=1), or drop --activity / vis.activity")
-    cp = getattr(model, "compute_path", None)
-    if cp is None:
+    fused, why = on_fused_engine(model)
+    if why is None:
         return (f"{type(model).__name__}.forward reports \"activity\": None (as in the reference, which logs the activity of the "
                 "FireNet family only): evaluate a FireNet (LIF / PLIF / XLIF / ALIF FireNet), or drop --activity / vis.activity")
-    if cp[0] != "fused":
-        return (f"[event_flow_amd] activity: {type(model).__name__} runs on the general path ({cp[1]}): its activity is not counted "
+    if not fused:
+        return (f"[event_flow_amd] activity: {type(model).__name__} runs on the general path ({why}): its activity is not counted "
                 "on the device (ActivityLog reads the spike words of the fused FireNet engine -- LIF / PLIF / XLIF / ALIF FireNets at "
                 "32 channels); using model(..., log=True) on the host instead, nine reads per pass, batch-wide fractions only")
     return None
 
 
-class Ring:
-    """The ring rule of a device log of `rows` rows (monitor.TrainMonitor's): pass s goes to row s % rows, and the owner drains
-    before the ring wraps.  Host arithmetic only."""
-
-    def __init__(self, rows, what="ActivityLog"):
-        self.rows, self.what = int(rows), what
-        if self.rows < 1:
-            raise _lib.EvflowError(f"{what}: a log of at least one row")
-        self.steps, self.drained = 0, 0
-
-    @property
-    def pending(self):
-        return self.steps - self.drained
-
-    @property
-    def full(self):
-        """The next pass would overwrite an undrained row."""
-        return self.pending >= self.rows
-
-    def next_row(self, ahead=1):
-        """The row the next pass fills.  Raises when the next `ahead` passes would reach a row that was not drained."""
-        if self.pending + ahead > self.rows:
-            raise _lib.EvflowError(f"{self.what}: {self.pending} undrained passes in a log of {self.rows} rows; call drain() before "
-                                   "the ring wraps")
-        return self.steps % self.rows
-
-    def advance(self, n=1):
-        self.steps += int(n)
-
-    def take(self):
-        """The rows written since the last drain, in pass order; they count as drained."""
-        if self.pending > self.rows:
-            raise _lib.EvflowError(f"{self.what}: {self.pending} passes since the last drain overwrote a log of {self.rows} rows")
-        idx = [s % self.rows for s in range(self.drained, self.steps)]
-        self.drained = self.steps
-        return idx
-
-
 class ActivityLog:
     """Per-pass activity counts of the nine FireNet layers, logged on the device (see the module).  The log is a ring of `rows`
-    rows (`Ring`); a stepper that knows its number of passes sizes it for them and never wraps."""
+    rows (`devlog.DeviceLog`); a stepper that knows its number of passes sizes it for them and never wraps."""
 
     def __init__(self, model, B, rows=1024):
         why = refusal(model)
@@ -140,10 +102,10 @@ class ActivityLog:
         self.model, self.B = model, int(B)
         if self.B < 1:
             raise _lib.EvflowError("ActivityLog: a batch of at least one sample")
-        self.ring = Ring(rows)
-        self.rows = self.ring.rows
+        # uint32 words, kept as int32 (the host reads them through a uint32 view); allocated by the first pass
+        self.dlog = DeviceLog(rows, None, torch.int32, -1, what="ActivityLog")
+        self.rows = self.dlog.rows
         self.shape = None  # (C, H, W) of the network input, known with the first pass
-        self.log = self._row = None
         model.keep_io(True)
 
     def close(self):
@@ -151,13 +113,14 @@ class ActivityLog:
         self.model.keep_io(False)
 
     # ------------------------------------------------------------------ ring
-    pending = property(lambda self: self.ring.pending)
-    full = property(lambda self: self.ring.full)
-    steps = property(lambda self: self.ring.steps)
+    pending = property(lambda self: self.dlog.ring.pending)
+    full = property(lambda self: self.dlog.ring.full)
+    steps = property(lambda self: self.dlog.ring.steps)
+    log = property(lambda self: self.dlog.log)
 
     def advance(self, n=1):
         """`n` passes were recorded through a row word of the caller's (a stepper's job table)."""
-        self.ring.advance(n)
+        self.dlog.ring.advance(n)
 
     def _allocate(self, x):
         if torch.cuda.is_current_stream_capturing():
@@ -171,9 +134,7 @@ class ActivityLog:
         self.parts = int(_lib.load().evf_activity_parts(max(self.n)))
         if self.parts < 1:
             raise _lib.EvflowError(f"evf_activity_parts refuses sources of up to {max(self.n)} elements (1 .. 2^27 - 1)")
-        # uint32 words, kept as int32 (the host reads them through a uint32 view)
-        self.log = torch.full((self.rows, len(LAYERS), self.B, self.parts), -1, dtype=torch.int32, device=x.device)
-        self._row = torch.zeros(1, dtype=torch.int64, device=x.device)  # eager passes: the log's own row word
+        self.dlog.allocate((len(LAYERS), self.B, self.parts), x.device)
         self._kind = (ctypes.c_int * len(LAYERS))(*KINDS)
         self._n = (ctypes.c_int64 * len(LAYERS))(*self.n)
 
@@ -200,28 +161,22 @@ class ActivityLog:
         words = [st[1] for st in states]
         if any(z.dtype != torch.int32 or tuple(z.shape) != (self.B, H, W) for z in words):
             raise _lib.EvflowError("ActivityLog: the spike words do not match the input")
-        if row_word is None:
-            self._row.fill_(self.ring.next_row())
-            word = _lib.ptr(self._row)
-        else:
-            word = row_word
+        self.dlog.use_row_word(row_word)
+        self.dlog.begin()
         src = [x] + words + [flow]
         _lib.call("evf_activity_at", (ctypes.c_void_p * len(LAYERS))(*[_lib.ptr(t) for t in src]), self._kind, self._n, len(LAYERS),
-                  self.B, word, int(row_mul), int(row_add), self.rows, _lib.ptr(self.log))
-        if row_word is None:
-            self.ring.advance()
+                  self.B, self.dlog.row_ptr(), int(row_mul), int(row_add), self.rows, _lib.ptr(self.log))
+        self.dlog.end()
         return src  # (inside a capture the caller keeps them allocated in the graph's pool)
 
     # ------------------------------------------------------------------ host
     def drain(self):
         """The counts of the passes recorded since the last drain, in pass order, as int64 [passes, 9, B]: one stream
         synchronise and one device -> host copy; the parts are added in int64."""
-        idx = self.ring.take()
-        if not idx or self.log is None:
+        rows = self.dlog.drain()
+        if rows is None:
             return np.empty((0, len(LAYERS), self.B), dtype=np.int64)
-        torch.cuda.current_stream().synchronize()
-        host = self.log.cpu().numpy().view(np.uint32)
-        return host[idx].astype(np.int64).sum(axis=3)
+        return rows.view(np.uint32).astype(np.int64).sum(axis=3)
 
     def fractions(self, counts):
         """`fractions` with this log's bits per layer."""
@@ -265,13 +220,7 @@ class ActivityCsv:
                 line += ["" if slots is None else self._fmt(slots[i][l][k]) for k in range(self.B) for l in range(len(LAYERS))]
             lines.append(line)
             self._pass += 1
-        os.makedirs(self.dir, exist_ok=True)
-        new = not os.path.exists(self.path)
-        with open(self.path, "a", newline="") as f:
-            w = csv.writer(f)
-            if new:
-                w.writerow(self.header)
-            w.writerows(lines)
+        append_csv(self.path, self.header, lines)
 
 
 class Report:

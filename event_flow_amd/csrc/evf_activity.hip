@@ -1,6 +1,6 @@
 // Spike-activity log of an evaluation pass (activity.ActivityLog): the reference's `model(..., log=True)` -- per layer the fraction
 // of nonzero outputs -- as EXACT integer counts, per source and per sample, appended to a device log at the row the host named
-// (the evf_aee_at conventions, evf_eval_log.hip).
+// (the device-log conventions, evf_log.h).
 //
 //   evf_activity_at   up to 16 sources [B][n_k] in ONE launch: float32 elements with x != 0 (EVF_ACT_FLOAT) or set bits of int32
 //                     words (EVF_ACT_WORDS) -> log[row][k][b][part], uint32.
@@ -8,7 +8,7 @@
 // One plain launch, no atomics, no ticket, no workspace: block (part, k, b) counts its contiguous share, reduces it in the block and
 // stores ONE word; the host adds the parts in int64.  Integer sums: the same bits from call to call.  Nothing is allocated or
 // copied, so the call can be captured.  A row outside 0 .. nrows - 1 leaves the log untouched.
-#include "evf_common.h"
+#include "evf_log.h"
 
 #define ACT_THREADS 256
 #define ACT_MAX_SRC 16
@@ -41,28 +41,12 @@ struct ActSrc {
   unsigned words;  // bit k: source k is EVF_ACT_WORDS
 };
 
-template <bool WORDS>
-__device__ __forceinline__ unsigned act_one(unsigned w) {
-  // FLOAT: torch.ne(0) on the bits -- -0.0 is zero, NaN, +-inf and every denormal are not, whatever the denormal mode
-  return WORDS ? (unsigned)__popc(w) : ((w & 0x7fffffffu) != 0u ? 1u : 0u);
-}
-
-// Elements [0, len) behind g (4-byte aligned): a scalar peel up to the first 16-byte boundary, 16-byte trips, a scalar tail.
+// Elements [0, len) behind g (4-byte aligned), counted by the 256 threads of a block (evf_walk16; four trips unrolled: the times
+// in the table above).
 template <bool WORDS>
 __device__ __forceinline__ unsigned act_count(const unsigned* __restrict__ g, int len) {
-  int head = (int)((4u - (unsigned)(((uintptr_t)g >> 2) & 3u)) & 3u);
-  head = head < len ? head : len;
-  const int n4 = (len - head) >> 2;
   unsigned cnt = 0;
-  if ((int)threadIdx.x < head) cnt += act_one<WORDS>(g[threadIdx.x]);
-  const uint4* g4 = (const uint4*)(g + head);
-#pragma unroll 4
-  for (int i = threadIdx.x; i < n4; i += ACT_THREADS) {
-    const uint4 q = g4[i];
-    cnt += act_one<WORDS>(q.x) + act_one<WORDS>(q.y) + act_one<WORDS>(q.z) + act_one<WORDS>(q.w);
-  }
-  const int t0 = head + 4 * n4;
-  if (t0 + (int)threadIdx.x < len) cnt += act_one<WORDS>(g[t0 + threadIdx.x]);  // (at most three)
+  evf_walk16<4>(g, len, (int)threadIdx.x, ACT_THREADS, true, [&](unsigned w) { cnt += act_one<WORDS>(w); });
   return cnt;
 }
 
@@ -71,8 +55,8 @@ __device__ __forceinline__ unsigned act_count(const unsigned* __restrict__ g, in
 __global__ void __launch_bounds__(ACT_THREADS) k_activity_at(ActSrc as, const long long* __restrict__ row, long long row_mul,
                                                              long long row_add, long long nrows, unsigned* __restrict__ log) {
   __shared__ unsigned red[ACT_THREADS / 64];
-  const __int128 r = (__int128)row[0] * row_mul + row_add;  // (128 bits: any row word times any row_mul is defined)
-  if (r < 0 || r >= nrows) return;
+  const long long r = evf_log_row(row, row_mul, row_add, nrows);
+  if (r < 0) return;
   const int parts = gridDim.x, p = blockIdx.x, k = blockIdx.y, b = blockIdx.z;
   const int n = as.n[k];
   const int share = (((n + parts - 1) / parts) + 3) & ~3;
@@ -83,12 +67,8 @@ __global__ void __launch_bounds__(ACT_THREADS) k_activity_at(ActSrc as, const lo
     const unsigned* g = as.src[k] + (long long)b * n + a;
     cnt = ((as.words >> k) & 1u) ? act_count<true>(g, len) : act_count<false>(g, len);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += (unsigned)__shfl_xor((int)cnt, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    log[((((long long)r * gridDim.y + k) * gridDim.z + b) * parts) + p] = ((red[0] + red[1]) + red[2]) + red[3];
+  cnt = evf_block_count(cnt, red);
+  if (threadIdx.x == 0) log[(((r * gridDim.y + k) * gridDim.z + b) * parts) + p] = cnt;
 }
 
 extern "C" int evf_activity_parts(int64_t n_max) {
@@ -99,9 +79,8 @@ extern "C" int evf_activity_parts(int64_t n_max) {
 
 extern "C" int evf_activity_at(const void* const* src, const int* kind, const int64_t* n, int nsrc, int B, const int64_t* row,
                                int64_t row_mul, int64_t row_add, int64_t nrows, uint32_t* log, void* stream) {
-  if (!src || !kind || !n || !row || !log) return EVF_EINVAL;
-  if (nsrc < 1 || nsrc > ACT_MAX_SRC || B < 1 || B > 65535 || nrows < 1 || row_mul < 0 || row_add < 0) return EVF_EINVAL;
-  if (((uintptr_t)log & 3u) || ((uintptr_t)row & 7u)) return EVF_EINVAL;
+  if (!src || !kind || !n || !evf_log_dest_ok(row, nrows, log)) return EVF_EINVAL;  // (the row is [nsrc][B][parts]: sized here)
+  if (nsrc < 1 || nsrc > ACT_MAX_SRC || B < 1 || B > 65535 || row_mul < 0 || row_add < 0) return EVF_EINVAL;
   ActSrc as;
   as.words = 0;
   int64_t n_max = 1;

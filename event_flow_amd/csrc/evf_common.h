@@ -88,11 +88,28 @@ __device__ __forceinline__ void evf_store_nt(float4* p, const float4 v) {
 }
 __device__ __forceinline__ void evf_store_nt(float* p, const float4 v) { evf_store_nt((float4*)p, v); }
 
-// wave64 sum, result valid in every lane
-__device__ __forceinline__ float evf_wave_sum(float v) {
+// wave64 butterfly of `op`, result valid in every lane
+template <typename T, typename Op>
+__device__ __forceinline__ T evf_wave_reduce(T v, Op op) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
   return v;
+}
+// ... as a sum (float, double: in butterfly order; unsigned: exact) and as the float minimum / maximum (fminf / fmaxf: a NaN is dropped)
+__device__ __forceinline__ float evf_wave_sum(float v) {
+  return evf_wave_reduce(v, [](float a, float b) { return a + b; });
+}
+__device__ __forceinline__ double evf_wave_sum(double v) {
+  return evf_wave_reduce(v, [](double a, double b) { return a + b; });
+}
+__device__ __forceinline__ unsigned evf_wave_sum(unsigned v) {
+  return evf_wave_reduce(v, [](unsigned a, unsigned b) { return a + b; });
+}
+__device__ __forceinline__ float evf_wave_min(float v) {
+  return evf_wave_reduce(v, [](float a, float b) { return fminf(a, b); });
+}
+__device__ __forceinline__ float evf_wave_max(float v) {
+  return evf_wave_reduce(v, [](float a, float b) { return fmaxf(a, b); });
 }
 
 // block-wide sum of up to 1024 threads; result valid in thread 0

@@ -6,14 +6,15 @@
 //   evf_aee_at             the AEE of one pass (evaluate.ResidentAEEStep) reduced and stored at log[row[0] * row_floats + offset ..].
 //
 // The first is a plain streaming copy: a row is K * (B + 1) + P floats (a few dozen), every segment one to B of them.
-#include "evf_common.h"
+// The row word, the no-op outside 0 .. nrows - 1 and the host's destination guard are evf_log.h's.
+#include "evf_log.h"
 
 // --------------------------------------------------------------------------
 // evf_store_segments_at
 // --------------------------------------------------------------------------
 // Block y = segment, a grid-stride loop of dword loads and stores over it (the destinations are only 4-byte aligned: the row
-// pitch and the offsets are arbitrary).  The row word is read once per block; a row outside 0 .. nrows - 1 returns before any
-// store.  offset[k] + n[k] <= row_floats is checked on the host, so an accepted row never writes outside the log.
+// pitch and the offsets are arbitrary).  A row outside 0 .. nrows - 1 returns before any store.  offset[k] + n[k] <= row_floats
+// is checked on the host, so an accepted row never writes outside the log.
 #define STORE_THREADS 256
 #define STORE_MAX_BLOCKS 64  // per segment
 struct StoreSegs {
@@ -23,10 +24,8 @@ struct StoreSegs {
 };
 __global__ void __launch_bounds__(STORE_THREADS) k_store_segments_at(const long long* __restrict__ row, long long nrows,
                                                                       float* __restrict__ log, long long row_floats, StoreSegs sg) {
-  __shared__ long long r;
-  if (threadIdx.x == 0) r = row[0];  // one load per block
-  __syncthreads();
-  if (r < 0 || r >= nrows) return;
+  const long long r = evf_log_row(row, 1, 0, nrows);
+  if (r < 0) return;
   const int k = blockIdx.y;
   const float* s = sg.src[k];
   float* d = log + r * row_floats + sg.offset[k];
@@ -132,8 +131,8 @@ __global__ void __launch_bounds__(AEE_THREADS) k_aee_stripes(const float* __rest
 __global__ void __launch_bounds__(AEE_THREADS) k_aee_finish(float* __restrict__ ws, int B, int S, const long long* __restrict__ row,
                                                             long long nrows, float* __restrict__ log, long long row_floats,
                                                             int offset) {
-  const long long r = row[0];
-  if (r < 0 || r >= nrows) return;
+  const long long r = evf_log_row(row, 1, 0, nrows);
+  if (r < 0) return;
   for (int b = threadIdx.x; b < B; b += AEE_THREADS) {
     float* w = ws + (long)b * S * 3;
     float se = 0.f, nv = 0.f, no = 0.f;
@@ -172,14 +171,14 @@ extern "C" int evf_aee_at_stripes(int H, int W) {
 extern "C" int evf_aee_at(const float* flow, const float* gt, const float* mask, const double* dt_gt, const double* dt_input, int B,
                           int H, int W, float flow_scaling, const int64_t* row, int64_t nrows, float* log, int64_t row_floats,
                           int offset, float* ws, int64_t ws_floats, void* stream) {
-  if (!flow || !gt || !mask || !dt_gt || !dt_input || !row || !log || !ws) return EVF_EINVAL;
-  if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || nrows <= 0 || row_floats <= 0 || offset < 0) return EVF_EINVAL;
+  if (!flow || !gt || !mask || !dt_gt || !dt_input || !ws) return EVF_EINVAL;
+  if (B <= 0 || B > 65535 || H <= 0 || W <= 0) return EVF_EINVAL;
+  if (!evf_log_dest_ok(row, nrows, log, row_floats, offset, 2 * ((int64_t)B + 1))) return EVF_EINVAL;
   const int S = evf_aee_at_stripes(H, W);
   if (S < 1 || S > 65535) return EVF_EINVAL;
-  if ((int64_t)offset + 2 * ((int64_t)B + 1) > row_floats) return EVF_EINVAL;
   if (ws_floats < (int64_t)B * S * 3) return EVF_EINVAL;
-  if (((uintptr_t)log & 3u) || ((uintptr_t)ws & 3u) || ((uintptr_t)flow & 3u) || ((uintptr_t)gt & 3u) || ((uintptr_t)mask & 3u) ||
-      ((uintptr_t)dt_gt & 7u) || ((uintptr_t)dt_input & 7u) || ((uintptr_t)row & 7u))
+  if (((uintptr_t)ws & 3u) || ((uintptr_t)flow & 3u) || ((uintptr_t)gt & 3u) || ((uintptr_t)mask & 3u) || ((uintptr_t)dt_gt & 7u) ||
+      ((uintptr_t)dt_input & 7u))
     return EVF_EINVAL;
   const int HW = H * W;
   const bool vec = (W % 4 == 0) && !(((uintptr_t)flow | (uintptr_t)gt | (uintptr_t)mask) & 15u);

@@ -1,6 +1,6 @@
 // Training log of a (replayed) optimizer step (monitor.TrainMonitor): what the reference's vis.store_grads records per step --
 // mean, min and max of |grad| per weight tensor after clipping -- and the spike rate of every layer of the fused FireNets, appended
-// to a preallocated device log at the row the host named in the step's job table (the evf_aee_at conventions, evf_eval_log.hip).
+// to a preallocated device log at the row the host named in the step's job table (the device-log conventions, evf_log.h).
 //
 //   evf_grad_stats_partial   BEFORE the optimizer step (which clears the gradient): per segment and chunk of GS_CHUNK elements
 //                            (float64 sum |g|, min |g|, max |g|, NaN seen) -> ws[segment][chunk].
@@ -12,7 +12,7 @@
 //
 // Plain launches on one stream, no atomics, no ticket: every addition's order is fixed by the geometry, so two calls give the same
 // bits; nothing is allocated or copied, so the calls can be captured.  A row word outside 0 .. nrows - 1 leaves the log untouched.
-#include "evf_common.h"
+#include "evf_log.h"
 
 #define GS_THREADS 256
 #define GS_CHUNK 4096  // elements per block: 16 per thread
@@ -22,28 +22,6 @@
 #define SC_THREADS 256
 #define SC_PARTS 32  // blocks (and partials) per source
 #define SC_MAX_SLOTS 256
-
-// wave64 reductions, result valid in every lane (the float sum is evf_wave_sum)
-__device__ __forceinline__ double tl_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float tl_wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float tl_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ unsigned tl_wave_sum(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
-  return v;
-}
 
 // --------------------------------------------------------------------------
 // evf_grad_stats_partial
@@ -60,9 +38,9 @@ __device__ __forceinline__ void gs_take(float x, GsAcc& a) {
   a.hi = fmaxf(a.hi, m);
 }
 
-// Block (c, k): elements [c * GS_CHUNK, min((c + 1) * GS_CHUNK, n_k)) of segment k.  The segment starts anywhere: a scalar peel up
-// to the first 16-byte boundary, float4 trips, a scalar tail.  A block past its segment's end leaves at once (its ws entry is
-// never read).  Every other block writes its entry: ws needs no clearing.
+// Block (c, k): elements [c * GS_CHUNK, min((c + 1) * GS_CHUNK, n_k)) of segment k.  The segment starts anywhere: evf_walk16.
+// A block past its segment's end leaves at once (its ws entry is never read).  Every other block writes its entry: ws needs no
+// clearing.
 __global__ void __launch_bounds__(GS_THREADS) k_grad_stats_partial(const float* __restrict__ grad, const long long* __restrict__ seg_off,
                                                                    const long long* __restrict__ seg_n, long long max_n,
                                                                    float* __restrict__ ws) {
@@ -76,25 +54,11 @@ __global__ void __launch_bounds__(GS_THREADS) k_grad_stats_partial(const float* 
   if (a >= n) return;
   const long long b = a + GS_CHUNK < n ? a + GS_CHUNK : n;
   const float* g = grad + seg_off[k] + a;
-  const int len = (int)(b - a);
-  int head = (int)((4u - (unsigned)(((uintptr_t)g >> 2) & 3u)) & 3u);
-  head = head < len ? head : len;
-  const int n4 = (len - head) >> 2;
   GsAcc acc = {0.0, INFINITY, 0.f, 0.f};
-  if ((int)threadIdx.x < head) gs_take(g[threadIdx.x], acc);
-  const float4* g4 = (const float4*)(g + head);
-  for (int i = threadIdx.x; i < n4; i += GS_THREADS) {
-    const float4 q = g4[i];
-    gs_take(q.x, acc);
-    gs_take(q.y, acc);
-    gs_take(q.z, acc);
-    gs_take(q.w, acc);
-  }
-  const int t0 = head + 4 * n4;
-  if (t0 + (int)threadIdx.x < len) gs_take(g[t0 + threadIdx.x], acc);  // (at most three)
+  evf_walk16(g, (int)(b - a), (int)threadIdx.x, GS_THREADS, true, [&](float x) { gs_take(x, acc); });
   // wave butterflies, then the four waves in index order
-  const double ws_ = tl_wave_sum(acc.s);
-  const float wlo = tl_wave_min(acc.lo), whi = tl_wave_max(acc.hi);
+  const double ws_ = evf_wave_sum(acc.s);
+  const float wlo = evf_wave_min(acc.lo), whi = evf_wave_max(acc.hi);
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   if (lane == 0) dred[wid] = ws_, lred[wid] = wlo, hred[wid] = whi;
   const float nans = evf_block_sum(acc.nan, red);  // (its barriers publish dred / lred / hred as well)
@@ -141,8 +105,8 @@ __global__ void __launch_bounds__(GS_TILE) k_grad_stats_store(const float* __res
                                                               long long nrows, float* __restrict__ log, long long row_floats,
                                                               int offset) {
   __shared__ float st[GS_TILE][GS_WORDS];
-  const long long r = row[0];
-  if (r < 0 || r >= nrows) return;
+  const long long r = evf_log_row(row, 1, 0, nrows);
+  if (r < 0) return;
   const float total = norm_ws[0];
   float coef = 1.f;
   if (max_norm > 0.f) coef = fminf(1.f, max_norm / (sqrtf(total) + 1e-6f));
@@ -191,14 +155,11 @@ __global__ void __launch_bounds__(GS_TILE) k_grad_stats_store(const float* __res
 extern "C" int evf_grad_stats_store(const float* ws, int64_t ws_floats, const int64_t* seg_n, int nseg, int64_t max_n,
                                     const float* norm_ws, float max_norm, const float* loss, const int64_t* row, int64_t nrows,
                                     float* log, int64_t row_floats, int offset, void* stream) {
-  if (!ws || !seg_n || !norm_ws || !row || !log) return EVF_EINVAL;  // (loss may be NULL: the field is left as it is)
-  if (nrows <= 0 || row_floats <= 0 || offset < 0) return EVF_EINVAL;
+  if (!ws || !seg_n || !norm_ws) return EVF_EINVAL;  // (loss may be NULL: the field is left as it is)
   const int64_t need = evf_grad_stats_ws(nseg, max_n);
   if (need < 0 || ws_floats < need) return EVF_EINVAL;
-  if ((int64_t)offset + 3 + 3 * (int64_t)nseg > row_floats) return EVF_EINVAL;
-  if (((uintptr_t)ws & 3u) || ((uintptr_t)log & 3u) || ((uintptr_t)norm_ws & 3u) || ((uintptr_t)loss & 3u) || ((uintptr_t)seg_n & 7u) ||
-      ((uintptr_t)row & 7u))
-    return EVF_EINVAL;
+  if (!evf_log_dest_ok(row, nrows, log, row_floats, offset, 3 + 3 * (int64_t)nseg)) return EVF_EINVAL;
+  if (((uintptr_t)ws & 3u) || ((uintptr_t)norm_ws & 3u) || ((uintptr_t)loss & 3u) || ((uintptr_t)seg_n & 7u)) return EVF_EINVAL;
   hipLaunchKernelGGL(k_grad_stats_store, dim3(nseg + 1), dim3(GS_TILE), 0, EVF_STREAM(stream), ws, (const long long*)seg_n, nseg,
                      (long long)max_n, evf_cdiv(max_n, GS_CHUNK), norm_ws, max_norm, loss, (const long long*)row, (long long)nrows, log,
                      (long long)row_floats, offset);
@@ -208,33 +169,19 @@ extern "C" int evf_grad_stats_store(const float* ws, int64_t ws_floats, const in
 // --------------------------------------------------------------------------
 // evf_spike_count
 // --------------------------------------------------------------------------
-// Block (p, k): part p of source k, a grid-stride loop over the source's 16-byte groups behind a scalar peel (a source is only
-// 4-byte aligned); block 0 of a source also takes the peel and the tail.  Every block stores its partial (0 when it had nothing):
-// ws needs no clearing.  A partial is at most n_words * 32 / SC_PARTS + 7 * 32 < 2^32.
+// Block (p, k): part p of source k, a grid-stride loop over the source's 16-byte groups (evf_walk16); block 0 of a source also
+// takes the peel and the tail.  Every block stores its partial (0 when it had nothing): ws needs no clearing.  A partial is at most n_words * 32 / SC_PARTS + 7 * 32 < 2^32.
 struct ScSrc {
-  const int* src[32];
+  const unsigned* src[32];
 };
 __global__ void __launch_bounds__(SC_THREADS) k_spike_count(ScSrc sc, long long n_words, unsigned* __restrict__ ws, int slot0) {
   __shared__ unsigned red[SC_THREADS / 64];
   const int k = blockIdx.y;
-  const int* s = sc.src[k];
-  long long head = (long long)((4u - (unsigned)(((uintptr_t)s >> 2) & 3u)) & 3u);
-  head = head < n_words ? head : n_words;
-  const long long n4 = (n_words - head) >> 2, t0 = head + 4 * n4;
   unsigned cnt = 0;
-  const int4* s4 = (const int4*)(s + head);
-  for (long long i = (long long)blockIdx.x * SC_THREADS + threadIdx.x; i < n4; i += (long long)SC_PARTS * SC_THREADS) {
-    const int4 q = s4[i];
-    cnt += __popc((unsigned)q.x) + __popc((unsigned)q.y) + __popc((unsigned)q.z) + __popc((unsigned)q.w);
-  }
-  if (blockIdx.x == 0) {
-    if ((long long)threadIdx.x < head) cnt += __popc((unsigned)s[threadIdx.x]);
-    if (t0 + threadIdx.x < n_words) cnt += __popc((unsigned)s[t0 + threadIdx.x]);  // (at most three)
-  }
-  cnt = tl_wave_sum(cnt);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) ws[(long long)(slot0 + k) * SC_PARTS + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  evf_walk16(sc.src[k], n_words, (long long)blockIdx.x * SC_THREADS + threadIdx.x, (long long)SC_PARTS * SC_THREADS, blockIdx.x == 0,
+             [&](unsigned w) { cnt += act_one<true>(w); });
+  cnt = evf_block_count(cnt, red);
+  if (threadIdx.x == 0) ws[(long long)(slot0 + k) * SC_PARTS + blockIdx.x] = cnt;
 }
 
 extern "C" int evf_spike_count_parts() { return SC_PARTS; }
@@ -247,7 +194,7 @@ extern "C" int evf_spike_count(const void* const* src, int nsrc, int64_t n_words
     sc.src[k] = nullptr;
     if (k >= nsrc) continue;
     if (!src[k] || ((uintptr_t)src[k] & 3u)) return EVF_EINVAL;
-    sc.src[k] = (const int*)src[k];
+    sc.src[k] = (const unsigned*)src[k];
   }
   hipLaunchKernelGGL(k_spike_count, dim3(SC_PARTS, nsrc), dim3(SC_THREADS), 0, EVF_STREAM(stream), sc, (long long)n_words, (unsigned*)ws,
                      slot0);
@@ -266,8 +213,8 @@ __global__ void __launch_bounds__(SC_MAX_SLOTS) k_spike_rates_store(const unsign
                                                                     long long total, const long long* __restrict__ row,
                                                                     long long nrows, float* __restrict__ log, long long row_floats,
                                                                     int offset) {
-  const long long r = row[0];
-  if (r < 0 || r >= nrows) return;
+  const long long r = evf_log_row(row, 1, 0, nrows);
+  if (r < 0) return;
   const int l = threadIdx.x;
   if (l >= nlayers) return;
   long long cnt = 0;
@@ -281,11 +228,9 @@ __global__ void __launch_bounds__(SC_MAX_SLOTS) k_spike_rates_store(const unsign
 extern "C" int evf_spike_rates_store(const void* ws, int ws_slots, const int* slot_layer, int nslots, int nlayers,
                                      int64_t total_bits_per_layer, const int64_t* row, int64_t nrows, float* log, int64_t row_floats,
                                      int offset, void* stream) {
-  if (!ws || !slot_layer || !row || !log) return EVF_EINVAL;
+  if (!ws || !slot_layer || ((uintptr_t)ws & 3u)) return EVF_EINVAL;
   if (nslots < 1 || nslots > SC_MAX_SLOTS || nlayers < 1 || nlayers > SC_MAX_SLOTS || ws_slots < nslots) return EVF_EINVAL;
-  if (total_bits_per_layer <= 0 || nrows <= 0 || row_floats <= 0 || offset < 0 || (int64_t)offset + nlayers > row_floats)
-    return EVF_EINVAL;
-  if (((uintptr_t)ws & 3u) || ((uintptr_t)log & 3u) || ((uintptr_t)row & 7u)) return EVF_EINVAL;
+  if (total_bits_per_layer <= 0 || !evf_log_dest_ok(row, nrows, log, row_floats, offset, nlayers)) return EVF_EINVAL;
   ScLayers sl;
   for (int s = 0; s < SC_MAX_SLOTS; ++s) {
     sl.layer[s] = 0xff;

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from .dataloader.resident import ResidentWindow, zero_states_if
+from .devlog import on_fused_engine
 from .utils.iwe import compute_pol_iwe
 
 AEE_MODES = ("gtflow_dt1", "gtflow_dt4")  # the ground-truth modes: AEE alone is replayed pass by pass (ResidentAEEStep)
@@ -46,10 +47,10 @@ def graphed_refusal(args, config, model=None):
         return ("--graphed evaluates FWL / RSAT in data.mode 'events'; AEE needs a ground-truth mode (gtflow_dt1 / gtflow_dt4 with "
                 "metrics.name [AEE]): drop --graphed")
     if model is not None:
-        path = getattr(model, "compute_path", ("general", "no fused FireNet engine"))
-        if path[0] != "fused":
+        fused, why = on_fused_engine(model)
+        if not fused:
             return (f"--graphed needs a network on the fused FireNet engine; {type(model).__name__} runs on the general path "
-                    f"({path[1]}): use --resident without --graphed")
+                    f"({'no fused FireNet engine' if why is None else why}): use --resident without --graphed")
     return None
 
 
@@ -86,6 +87,23 @@ def row_layout(K, B, P):
     return K * (B + 1) + P
 
 
+def sum_metric_rows(out, host, names, B, row_files=None):
+    """Into `out`: per metric k of `names` the logged batch means host[r][k * (B + 1) + B] summed as Python floats in row order
+    and divided by max(rows, 1); `row_files[r][b]`: the file slot b reads at row r -> the per-slot values by file as
+    "per_sequence" as well.  `host`: the rows as lists of Python floats."""
+    per = PerSequence() if row_files is not None else None
+    for k, name in enumerate(names):
+        total = 0.0
+        for r, row in enumerate(host):
+            total += row[k * (B + 1) + B]
+            if per is not None:
+                per.add(name, row_files[r], row[k * (B + 1):k * (B + 1) + B])
+        out[name] = total / max(len(host), 1)
+    if per is not None:
+        out["per_sequence"] = per.summary()
+    return out
+
+
 def reduce_eval_log(log, tail_sharp, names, B, P, row_files=None):
     """The eager driver's accumulation over a result log [rows, row_layout(K, B, P)] (float32, any device) and the sharpness
     scalars of the tail passes (float32 [n], same device): the metrics are summed as Python floats in row order from the
@@ -93,23 +111,10 @@ def reduce_eval_log(log, tail_sharp, names, B, P, row_files=None):
     scalars in pass order, taken on the log's device (torch.stack([...]).mean() of the eager loop).  `row_files[r][b]`: the file
     slot b reads at row r -> "per_sequence" as well.  ONE device -> host read of the log."""
     K = len(names)
-    rows = log.shape[0]
     if log.shape[1] != row_layout(K, B, P):
         raise _lib.EvflowError(f"result log rows of {log.shape[1]} floats, expected {row_layout(K, B, P)}")
     sharp = torch.cat([log[:, K * (B + 1):].reshape(-1), tail_sharp.reshape(-1).to(log.dtype)])
-    host = log.cpu().tolist()
-    out = {"iwe_variance": float(sharp.mean())}
-    per = PerSequence() if row_files is not None else None
-    for k, name in enumerate(names):
-        total = 0.0
-        for r in range(rows):
-            total += host[r][k * (B + 1) + B]
-            if per is not None:
-                per.add(name, row_files[r], host[r][k * (B + 1):k * (B + 1) + B])
-        out[name] = total / max(rows, 1)
-    if per is not None:
-        out["per_sequence"] = per.summary()
-    return out
+    return sum_metric_rows({"iwe_variance": float(sharp.mean())}, log.cpu().tolist(), names, B, row_files)
 
 
 class _ReplayedSteps:
@@ -123,8 +128,9 @@ class _ReplayedSteps:
         for name in ("state_buffers", "set_state_buffers", "final_states_into", "mark_last_pass"):
             if not hasattr(model, name):
                 raise _lib.EvflowError(f"{what} needs a model with the fused FireNet engine")
-        if getattr(model, "compute_path", ("general", ""))[0] != "fused":
-            raise _lib.EvflowError(f"{what} needs a network on the fused FireNet engine ({model.compute_path[1]})")
+        fused, why = on_fused_engine(model)
+        if not fused:
+            raise _lib.EvflowError(f"{what} needs a network on the fused FireNet engine ({why})")
         self.model, self.replay = model, bool(replay)
         self.warmup, self.seen = max(int(warmup), 2), 0
         self.stream = torch.cuda.Stream()
@@ -467,17 +473,6 @@ class ResidentAEEStep(_ReplayedSteps):
         order from the logged batch means and divided by max(it, 1); iwe_variance the mean of the one contiguous float32 vector
         of the passes' sharpness scalars, taken on the device; with `per_sequence` the per-slot values by file."""
         torch.cuda.current_stream().wait_stream(self.stream)
-        B, it = self.B, self.evaluated
         out = {"iwe_variance": float(self.sharp_log[:self.seen].mean())}
-        host = self.aee_log[:it].cpu().tolist()
-        per = PerSequence() if self.row_files is not None else None
-        for k, name in enumerate(("AEE", "AEE_percent_outliers")):
-            total = 0.0
-            for r in range(it):
-                total += host[r][k * (B + 1) + B]
-                if per is not None:
-                    per.add(name, self.row_files[r], host[r][k * (B + 1):k * (B + 1) + B])
-            out[name] = total / max(it, 1)
-        if per is not None:
-            out["per_sequence"] = per.summary()
-        return self._activity_results(out, per is not None)
+        sum_metric_rows(out, self.aee_log[:self.evaluated].cpu().tolist(), ("AEE", "AEE_percent_outliers"), self.B, self.row_files)
+        return self._activity_results(out, self.row_files is not None)

@@ -15,7 +15,6 @@ word in device memory -- the monitor's own for eager steps, a word of the step's
 `CsvLog` writes drained rows as `grads_w.csv` (the reference's `save_csv` layout) and `train_log.csv`.
 """
 
-import csv
 import ctypes
 import os
 import sys
@@ -23,10 +22,11 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, activity
+from .devlog import DeviceLog, append_csv, on_fused_engine
 
 HEAD = ("loss", "grad_norm", "clip_coef")
-LAYERS = ("1:head", "2:G1", "3:R1a", "4:R1b", "5:G2", "6:R2a", "7:R2b")  # the names of model(..., log=True)
+LAYERS = activity.LAYERS[1:8]  # the seven spiking layers, by the names of model(..., log=True)
 MAX_SLOTS = 256  # (layer, pass) spike tensors of one window (evf_spike_rates_store)
 
 
@@ -45,14 +45,15 @@ def weight_segments(model):
 
 
 def has_spike_rates(model):
-    return getattr(model, "compute_path", ("general", ""))[0] == "fused"
+    return on_fused_engine(model)[0]
 
 
 def rates_notice(model):
     """What the monitor says once about a network whose spike rates it cannot log (None: it logs them)."""
-    if has_spike_rates(model):
+    fused, why = on_fused_engine(model)
+    if fused:
         return None
-    why = getattr(model, "compute_path", ("general", "no FireNet-family network"))[1]
+    why = "no FireNet-family network" if why is None else why
     return (f"[event_flow_amd] TrainMonitor: {type(model).__name__} runs on the general path ({why}): gradient statistics only, no "
             "rate/<layer> columns -- spike rates are counted from the spike words of the fused FireNet engine (LIF / PLIF / XLIF / "
             "ALIF FireNets at 32 channels); model(..., log=True) reports a general-path network's activity pass by pass")
@@ -89,8 +90,8 @@ def refusal(optimizer=None, fused_optimizer=None, want_rates=False):
 class TrainMonitor:
     """Gradient statistics and spike rates of every optimizer step, logged on the device (see the module).
 
-    The log is a ring of `rows` rows: step s goes to row s % rows, and the owner drains before the ring wraps (`pending`,
-    `full`).  Spike rates exist only for a network on the fused FireNet engine (`model.compute_path[0] == "fused"`); on the
+    The log is a ring of `rows` rows (`devlog.DeviceLog`): the owner drains before the ring wraps (`pending`, `full`).  Spike
+    rates exist only for a network on the fused FireNet engine (`model.compute_path[0] == "fused"`); on the
     general path the monitor logs gradients only and says so once."""
 
     def __init__(self, model, optimizer, rows=1024):
@@ -98,9 +99,6 @@ class TrainMonitor:
         if why:
             raise _lib.EvflowError(why)
         self.model, self.opt = model, optimizer
-        self.rows = int(rows)
-        if self.rows < 1:
-            raise _lib.EvflowError("TrainMonitor: a log of at least one row")
         self.segments = weight_segments(model)
         if not self.segments:
             raise _lib.EvflowError("TrainMonitor: the model has no trainable parameter whose name contains 'weight'")
@@ -116,7 +114,8 @@ class TrainMonitor:
         lib = _lib.load()
         self.nseg = len(self.segments)
         self.max_n = max(n for _name, _off, n in self.segments)
-        self.log = torch.full((self.rows, self.row_floats), float("nan"), dtype=torch.float32, device=dev)
+        self.dlog = DeviceLog(rows, (self.row_floats,), torch.float32, float("nan"), dev, "TrainMonitor")
+        self.rows, self.log = self.dlog.rows, self.dlog.log
         self.seg_off = torch.tensor([off for _name, off, _n in self.segments], dtype=torch.int64, device=dev)
         self.seg_n = torch.tensor([n for _name, _off, n in self.segments], dtype=torch.int64, device=dev)
         need = int(lib.evf_grad_stats_ws(self.nseg, self.max_n))
@@ -124,10 +123,7 @@ class TrainMonitor:
             raise _lib.EvflowError(f"evf_grad_stats_ws({self.nseg}, {self.max_n}) failed with status {need}")
         self.grad_ws = torch.empty(need, dtype=torch.float32, device=dev)
         self.spike_ws = torch.empty((MAX_SLOTS, int(lib.evf_spike_count_parts())), dtype=torch.int32, device=dev) if self.rates else None
-        self._row = torch.zeros(1, dtype=torch.int64, device=dev)  # eager steps: the monitor's own row word
-        self._row_ptr = None  # ... or a word of the step's job table (use_row_word)
         self._slot_layer = None  # the window's counted slots, between count_spikes and after_step
-        self.steps, self.drained = 0, 0
         if self.rates:
             model._eng()._spike_taps = []
 
@@ -140,30 +136,22 @@ class TrainMonitor:
     def columns(self):
         return list(self._columns)
 
-    # ------------------------------------------------------------------ row word
+    # ------------------------------------------------------------------ ring and row word (the log's)
+    pending = property(lambda self: self.dlog.ring.pending)
+    full = property(lambda self: self.dlog.ring.full)
+    steps = property(lambda self: self.dlog.ring.steps)
+
     def use_row_word(self, ptr):
         """The row of every following step is read from the int64 word at device address `ptr` (a word of the step's job table,
         written by the stepper, which also calls `advance()`); None: back to the monitor's own word."""
-        self._row_ptr = ptr
+        self.dlog.use_row_word(ptr)
 
     def next_row(self):
         """The row the next step fills.  Raises when that row still holds a step that was not drained."""
-        if self.pending >= self.rows:
-            raise _lib.EvflowError(f"TrainMonitor: {self.pending} undrained steps in a log of {self.rows} rows; call drain() before "
-                                   "the ring wraps")
-        return self.steps % self.rows
+        return self.dlog.ring.next_row()
 
     def advance(self):
-        self.steps += 1
-
-    @property
-    def pending(self):
-        return self.steps - self.drained
-
-    @property
-    def full(self):
-        """The next step would overwrite an undrained row."""
-        return self.pending >= self.rows
+        self.dlog.ring.advance()
 
     # ------------------------------------------------------------------ launches (all capturable)
     def begin_window(self):
@@ -198,15 +186,14 @@ class TrainMonitor:
 
     def before_step(self):
         """Before `optimizer.step()`, which clears the gradient: evf_grad_stats_partial."""
-        if self._row_ptr is None:
-            self._row.fill_(self.next_row())
+        self.dlog.begin()
         _lib.call("evf_grad_stats_partial", _lib.ptr(self.opt.flat_grad), _lib.ptr(self.seg_off), _lib.ptr(self.seg_n), self.nseg,
                   self.max_n, _lib.ptr(self.grad_ws), self.grad_ws.numel())
 
     def after_step(self, loss):
         """After `optimizer.step()`, so that the logged norm and coefficient are the applied ones: evf_grad_stats_store and
         evf_spike_rates_store into the step's row."""
-        row = self._row_ptr if self._row_ptr is not None else _lib.ptr(self._row)
+        row = self.dlog.row_ptr()
         clip = self.opt.clip
         _lib.call("evf_grad_stats_store", _lib.ptr(self.grad_ws), self.grad_ws.numel(), _lib.ptr(self.seg_n), self.nseg, self.max_n,
                   _lib.ptr(self.opt.norm_ws), float(clip) if clip is not None else 0.0,
@@ -218,20 +205,14 @@ class TrainMonitor:
             sl, self._slot_layer = self._slot_layer, None
             _lib.call("evf_spike_rates_store", _lib.ptr(self.spike_ws), MAX_SLOTS, (ctypes.c_int * MAX_SLOTS)(*sl), len(sl),
                       len(LAYERS), self._total_bits, row, self.rows, _lib.ptr(self.log), self.row_floats, self.rate_offset)
-        if self._row_ptr is None:
-            self.advance()
+        self.dlog.end()
 
     # ------------------------------------------------------------------ host
     def drain(self):
         """The rows written since the last drain, in step order, as a numpy array [n, len(columns())]: one device -> host copy
         behind a stream synchronise."""
-        if self.pending > self.rows:
-            raise _lib.EvflowError(f"TrainMonitor: {self.pending} steps since the last drain overwrote a log of {self.rows} rows")
-        torch.cuda.current_stream().synchronize()
-        host = self.log.cpu().numpy()
-        idx = [s % self.rows for s in range(self.drained, self.steps)]
-        self.drained = self.steps
-        return host[idx].copy() if idx else np.empty((0, self.row_floats), dtype=np.float32)
+        rows = self.dlog.drain()
+        return rows if rows is not None else np.empty((0, self.row_floats), dtype=np.float32)
 
 
 class CsvLog:
@@ -253,16 +234,6 @@ class CsvLog:
     def _fmt(v):
         return "%.9g" % float(v)
 
-    def _append(self, name, header, lines):
-        os.makedirs(self.dir, exist_ok=True)
-        path = os.path.join(self.dir, name)
-        new = not os.path.exists(path)
-        with open(path, "a", newline="") as f:
-            w = csv.writer(f)
-            if new:
-                w.writerow(header)
-            w.writerows(lines)
-
     def write(self, epoch, rows):
         """Append `rows` (numpy [n, len(names)], the steps of `epoch` in order); the step index restarts with every epoch."""
         if epoch != self._epoch:
@@ -273,6 +244,6 @@ class CsvLog:
             logs.append([epoch, self._step] + [self._fmt(r[i]) for i in self.log_idx])
             self._step += 1
         if grads and self.grad_idx:
-            self._append("grads_w.csv", self.grad_header, grads)
+            append_csv(os.path.join(self.dir, "grads_w.csv"), self.grad_header, grads)
         if logs and self.log_idx:
-            self._append("train_log.csv", self.log_header, logs)
+            append_csv(os.path.join(self.dir, "train_log.csv"), self.log_header, logs)

@@ -757,9 +757,10 @@ int evf_aee_at(const float* flow, const float* gt, const float* mask, const doub
 
 /* Training log (csrc/evf_train_log.hip, monitor.TrainMonitor): the reference's vis.store_grads (utils/gradients.py get_grads: mean,
  * min and max of |grad| per weight tensor after clipping, train_flow.py:159-160) and the spike rate of every layer, stored into a
- * row of a device log by plain launches on one stream -- the evf_aee_at conventions: row is ONE int64 word in DEVICE memory,
- * read by the kernels, a word outside 0 .. nrows - 1 is a defined no-op on the log; no atomics, no ticket, the same bits from call
- * to call; nothing is allocated or copied, so the calls can be captured.  Every violation below is EVF_EINVAL before any launch.
+ * row of a device log by plain launches on one stream -- the device-log conventions, defined once in csrc/evf_log.h and shared
+ * with evf_store_segments_at, evf_aee_at and evf_activity_at: row is ONE int64 word in DEVICE memory, read by the kernels, a word
+ * outside 0 .. nrows - 1 is a defined no-op on the log; no atomics, no ticket, the same bits from call to call; nothing is
+ * allocated or copied, so the calls can be captured.  Every violation below is EVF_EINVAL before any launch.
  *
  * evf_grad_stats_partial -- BEFORE the optimizer step (evf_clip_adam_* clear the gradient as they apply it).  grad: the flat
  * float32 gradient; seg_off / seg_n: DEVICE int64 arrays of nseg entries (element offset and length of every segment; the zoo's
@@ -808,7 +809,7 @@ int evf_spike_rates_store(const void* ws, int ws_slots, const int* slot_layer, i
 
 /* evf_activity_at (csrc/evf_activity.hip): the spike activity of ONE evaluation pass (activity.ActivityLog) -- what the
  * reference's model(..., log=True) reports, the nonzero outputs of every layer -- as exact integer counts per source and per
- * sample, stored into a row of a device log by ONE plain launch: the evf_aee_at conventions.  src / kind / n: HOST arrays of
+ * sample, stored into a row of a device log by ONE plain launch: the device-log conventions (csrc/evf_log.h).  src / kind / n: HOST arrays of
  * nsrc entries in 1..16, passed by value in the launch's arguments (the evf_add_segments convention), so the call allocates
  * nothing, copies nothing and can be captured.  Source k is device memory [B][n[k]], contiguous and 4-byte aligned (16-byte
  * loads behind a scalar peel to the first 16-byte boundary, a scalar tail; n[k] is any number in 1 .. 2^27 - 1, so that 32 bits

@@ -236,8 +236,9 @@ def _count(dev, n_words, ws, slot0, ws_slots):
     _lib.call("evf_spike_count", (ctypes.c_void_p * 32)(*[t.data_ptr() for t in dev]), len(dev), n_words, _lib.ptr(ws), slot0, ws_slots)
 
 
-@pytest.mark.parametrize("n_words", [1, 63, 64, 1000, 2 * 32 * 32])
-@pytest.mark.parametrize("nsrc", [1, 5, 32])
+# (5, 33975): 32 parts of 256 threads stride over 8192 groups of 16 bytes a trip; 33975 words are at least 8492 groups at each
+# of the four alignments of the five sources, so block 0 takes a second trip and the tail exists
+@pytest.mark.parametrize("nsrc,n_words", [(nsrc, n) for nsrc in (1, 5, 32) for n in (1, 63, 64, 1000, 2 * 32 * 32)] + [(5, 33975)])
 def test_spike_counts_and_rates(nsrc, n_words):
     parts = int(_lib.load().evf_spike_count_parts())
     host, dev, _keep = _spike_sources(nsrc, n_words, seed=nsrc * 10007 + n_words)
