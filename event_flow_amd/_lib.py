@@ -86,6 +86,10 @@ SIGNATURES = {
     # maps, M, idx, flags, B, H, W, out  /  frames, M, curr, next, flags, B, H, W, out
     "evf_gather_flowmaps": [P, I, P, P, I, I, I, P, P],
     "evf_gather_frames": [P, I, P, P, P, I, I, I, P, P],
+    # streaming inference (stream.py): staged chunk, n, device head word, ring columns, R  /  ring columns, R, device first,
+    # device appended word, flags, B, P, N, H, W, ev, dt_input
+    "evf_ring_append": [P, I, P, P, P, P, P, L, P],
+    "evf_ring_cut": [P, P, P, P, L, P, P, P, I, I, I, I, I, P, P, P],
 }
 
 # network entry points (added as the kernels land)

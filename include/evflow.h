@@ -894,6 +894,30 @@ int evf_gather_flowmaps(const float* maps, int M, const int* idx, const int* fla
 int evf_gather_frames(const uint8_t* frames, int M, const int* curr, const int* next, const int* flags, int B, int H, int W,
                       uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------ streaming inference
+ * (stream.py, csrc/evf_stream.hip): pushed events live in a device RING of R slots per column -- the arena's layout, xs, ys
+ * uint16, ts float64, ps uint8 -- where stream event e sits at slot e mod R.  Plain loads and stores, no atomics; head, first and
+ * appended are words in DEVICE memory read by the kernels, nothing is allocated or copied: both calls can be captured.
+ *
+ * evf_ring_append: the n events of one staged chunk -- ONE contiguous device buffer laid out ts (float64 [n]) | xs (uint16 [n]) |
+ * ys (uint16 [n]) | ps (uint8 [n]), 8-byte aligned so that every column is naturally aligned -- are stored to slots
+ * (head[0] + i) mod R, i < n.  head: ONE int64 word, the stream index of the chunk's first event; a negative word writes
+ * nothing.  n = 0 launches nothing.  EVF_EINVAL, before any launch: a null pointer, n < 0, n > R, R < 1, chunk, head or ts not
+ * 8-byte aligned, xs or ys not 2-byte aligned.
+ *
+ * evf_ring_cut: evf_seq_cut on the ring.  Job j = b * P + p takes the N events first[j] .. first[j] + N - 1 (int64 [B*P],
+ * ABSOLUTE stream indices), reads them at index mod R and writes the rows ev [B][P][N][4] and dt_input [P][B] of evf_seq_cut on a
+ * linear arena of the same events, bit for bit, flags [B*P] as there.  appended: ONE int64 word, the number of events pushed so
+ * far, so that the ring holds events [appended - R, appended): a job whose range does not lie inside it (partly overwritten,
+ * partly unwritten, first < 0, N > R) gives padding rows (p = 0) and dt_input 0 and reads nothing.  B * P <= 65535.
+ * EVF_EINVAL, before any launch: a null pointer, R < 1, a non-positive B, P, N, H or W, B * P > 65535, first or appended not
+ * 8-byte aligned, ev not 16-byte aligned. */
+int evf_ring_append(const void* chunk, int n, const int64_t* head, uint16_t* xs, uint16_t* ys, double* ts, uint8_t* ps, int64_t R,
+                    void* stream);
+int evf_ring_cut(const uint16_t* xs, const uint16_t* ys, const double* ts, const uint8_t* ps, int64_t R, const int64_t* first,
+                 const int64_t* appended, const int* flags, int B, int P, int N, int H, int W, float* ev, double* dt_input,
+                 void* stream);
+
 /* Window masks: out [B,1,H,W] = min(sum_p masks[B,P,H,W], 1) (loss/flow.py:149-150); masked mean of the
  * per-pass flow maps [B,P,2,H,W] -> [B,2,H,W], sum_p maps*mask / (sum_p mask + 1e-9) (loss/flow.py:443-452). */
 int evf_mask_union(const float* masks, int B, int P, int H, int W, float* out, void* stream);
