@@ -90,6 +90,10 @@ SIGNATURES = {
     # device appended word, flags, B, P, N, H, W, ev, dt_input
     "evf_ring_append": [P, I, P, P, P, P, P, L, P],
     "evf_ring_cut": [P, P, P, P, L, P, P, P, I, I, I, I, I, P, P, P],
+    # the rig (rig_stream.py): staged buffer, B, n, most, ring columns [B][R], R  /  ring columns, R, device first, appended,
+    # count, flags, B, Npad, H, W, ev, dt_input
+    "evf_rings_append": [P, I, I, I, P, P, P, P, L, P],
+    "evf_rings_cut_ragged": [P, P, P, P, L, P, P, P, P, I, I, I, I, P, P, P],
 }
 
 # network entry points (added as the kernels land)

@@ -917,6 +917,30 @@ int evf_ring_append(const void* chunk, int n, const int64_t* head, uint16_t* xs,
 int evf_ring_cut(const uint16_t* xs, const uint16_t* ys, const double* ts, const uint8_t* ps, int64_t R, const int64_t* first,
                  const int64_t* appended, const int* flags, int B, int P, int N, int H, int W, float* ev, double* dt_input,
                  void* stream);
+/* The rig (rig_stream.py): B <= 16 synchronised cameras, one ring each -- the four columns are [B][R], ring b starts at b * R.
+ *
+ * evf_rings_append: ONE push to the B rings in one launch.  staged: ONE contiguous, 8-byte aligned device buffer laid out head
+ * (int64 [B], camera b's stream index of its first event of this push) | off (int64 [B + 1], the prefix sums of the per-camera
+ * counts: off[0] = 0, off[B] = n) | ts (float64 [n]) | xs (uint16 [n]) | ys (uint16 [n]) | ps (uint8 [n]), the cameras' events
+ * concatenated in camera order.  Event i of camera b goes to slot (head[b] + i - off[b]) mod R of ring b.  n: all events of
+ * the push, most: the largest per-camera count -- both known on the host.  The kernel's own guards: a negative head word writes
+ * nothing for that camera; an offset table that does not ascend from 0 to n, or gives a camera more than R events, writes
+ * nothing at all.  n = 0 launches nothing.  EVF_EINVAL, before any launch: a null pointer, B outside [1, 16], n < 0, R < 1,
+ * most outside [0, min(n, R)] or n > B * most, staged or ts not 8-byte aligned, xs or ys not 2-byte aligned.
+ *
+ * evf_rings_cut_ragged: evf_seq_cut_ragged on the B rings.  Job b takes camera b's events first[b] .. first[b] + count[b] - 1
+ * (ABSOLUTE per-camera stream indices) from ring b at index mod R and writes rows 0 .. count[b] - 1 of ev [B][Npad][4] and
+ * dt_input [B] exactly as evf_seq_cut_ragged does on a linear arena of the same events; the rows behind are zero.  first,
+ * appended: int64 [B]; count, flags: int32 [B]; all device memory.  Ring b holds events [appended[b] - R, appended[b]).  A job
+ * with count <= 0, count > Npad, count > R, first < 0, first < appended - R or first + count > appended is all padding with
+ * dt_input 0 and reads nothing.  EVF_EINVAL, before any launch: a null pointer, R < 1, B outside [1, 16], a non-positive Npad,
+ * H or W, first, appended, ts or dt_input not 8-byte aligned, count or flags not 4-byte aligned, xs or ys not 2-byte aligned,
+ * ev not 16-byte aligned. */
+int evf_rings_append(const void* staged, int B, int n, int most, uint16_t* xs, uint16_t* ys, double* ts, uint8_t* ps, int64_t R,
+                     void* stream);
+int evf_rings_cut_ragged(const uint16_t* xs, const uint16_t* ys, const double* ts, const uint8_t* ps, int64_t R,
+                         const int64_t* first, const int64_t* appended, const int* count, const int* flags, int B, int Npad, int H,
+                         int W, float* ev, double* dt_input, void* stream);
 
 /* Window masks: out [B,1,H,W] = min(sum_p masks[B,P,H,W], 1) (loss/flow.py:149-150); masked mean of the
  * per-pass flow maps [B,P,2,H,W] -> [B,2,H,W], sum_p maps*mask / (sum_p mask + 1e-9) (loss/flow.py:443-452). */
